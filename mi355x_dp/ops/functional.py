@@ -636,6 +636,110 @@ def sgd_flat_(params, grads, momentum_buf, params_bf16, lr, momentum=0.0, dampen
               float(grad_scale), stream_of(params))
 
 
+# flat AdamW (csrc/kernels/optim.hip).  Device state block, float64:
+#   [0] step t  [1] lr  [2] total_norm  [3] clip coefficient
+#   [4] lr / bc1  [5] 1 / sqrt(bc2)  [6] grad_scale * coef  [7] lr * wd
+ADAMW_STATE_LEN = 8
+
+
+def grad_sqnorm_slots(numels) -> int:
+    """fp64 partial slots ``grad_sqnorm_`` needs for segments of these sizes (0 on the host)."""
+    lib = _lib.load(required=False)
+    if lib is None:
+        return 0
+    return sum(lib.mi_grad_sqnorm_blocks(int(n)) for n in numels)
+
+
+def grad_sqnorm_(segments, out, partials=None):
+    """``out[0]`` (float64, one element) = sum of squares over all fp32 ``segments``, accumulated in
+    fp64 and deterministic: block partials in fixed slots of ``partials`` (``grad_sqnorm_slots``
+    doubles), summed in a fixed order by one block.  The result stays on the device."""
+    segments = list(segments)
+    if not out.is_cuda:
+        with torch.no_grad():
+            s = torch.zeros((), dtype=torch.float64)
+            for x in segments:
+                xd = x.double().reshape(-1)
+                s = s + (xd * xd).sum()
+            out.reshape(-1)[0] = s
+        return out
+    lib = _lib.load(True)
+    blocks = [lib.mi_grad_sqnorm_blocks(x.numel()) for x in segments]
+    if partials is None:
+        partials = torch.empty(sum(blocks), dtype=torch.float64, device=out.device)
+    assert partials.dtype == torch.float64 and partials.numel() >= sum(blocks) and out.dtype == torch.float64
+    st, slot = stream_of(out), 0
+    for x, nb in zip(segments, blocks):
+        assert x.dtype == torch.float32 and x.is_contiguous()
+        _lib.call("mi_grad_sqnorm_partial", ptr(x), x.numel(), ctypes.c_void_p(partials.data_ptr() + 8 * slot), st)
+        slot += nb
+    _lib.call("mi_grad_sqnorm_final", ptr(partials), slot, ptr(out), st)
+    return out
+
+
+def adamw_prep_(state, sumsq, beta1, beta2, weight_decay, max_norm=None, grad_scale=1.0):
+    """Advance the device step counter and derive this step's scalars in ``state`` (layout above)
+    from ``state[1]`` (lr) and, when ``max_norm`` is given, the squared gradient norm ``sumsq``:
+    ``total_norm = grad_scale * sqrt(sumsq)``, ``coef = min(1, max_norm / (total_norm + 1e-6))``
+    (``torch.nn.utils.clip_grad_norm_``).  No host read."""
+    clip = max_norm is not None
+    if not state.is_cuda:
+        import math
+        with torch.no_grad():
+            t = float(state[0]) + 1.0
+            lr = float(state[1])
+            bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
+            coef = 1.0
+            if clip:
+                total = grad_scale * math.sqrt(float(sumsq.reshape(-1)[0]))
+                c = float(max_norm) / (total + 1e-6)
+                coef = 1.0 if c > 1.0 else c  # NaN stays NaN, like torch's clamp(max=1)
+                state[2] = total
+            state[0] = t
+            state[3] = coef
+            state[4] = lr / bc1
+            state[5] = 1.0 / math.sqrt(bc2)
+            state[6] = grad_scale * coef
+            state[7] = lr * weight_decay
+        return
+    assert state.dtype == torch.float64 and state.numel() >= ADAMW_STATE_LEN
+    _lib.call("mi_adamw_prep", ptr(state), ptr(sumsq) if clip else ptr(None), float(beta1), float(beta2),
+              float(weight_decay), float(max_norm) if clip else 0.0, float(grad_scale), int(clip), stream_of(state))
+
+
+def adamw_flat_(params, grads, exp_avg, exp_avg_sq, params_bf16, state, beta1, beta2, eps, decay_map=None,
+                unit_base=0):
+    """One fused AdamW update over flat fp32 buffers (+ bf16 compute-copy refresh) with the
+    per-step scalars of ``adamw_prep_``.  ``decay_map``: uint8, one byte per 64-element unit of the
+    whole flat buffer (nonzero: the unit decays), ``unit_base`` the unit index of ``params[0]``;
+    None decays everything."""
+    n = params.numel()
+    if decay_map is not None:
+        assert decay_map.dtype == torch.uint8 and decay_map.numel() >= unit_base + (n + 63) // 64
+    if not params.is_cuda:
+        with torch.no_grad():
+            s = state.tolist()
+            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
+            g = grads * f32(s[6])
+            decayed = params * f32(1.0 - s[7])
+            if decay_map is None:
+                params.copy_(decayed)
+            else:
+                units = decay_map[unit_base:unit_base + (n + 63) // 64] != 0
+                params.copy_(torch.where(units.repeat_interleave(64)[:n], decayed, params))
+            exp_avg.mul_(beta1).add_(g, alpha=1 - beta1)
+            exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1 - beta2)
+            denom = exp_avg_sq.sqrt().mul_(f32(s[5])).add_(eps)
+            params.addcdiv_(exp_avg, denom, value=-f32(s[4]))
+            if params_bf16 is not None:
+                params_bf16.copy_(params)
+        return
+    for t in (params, grads, exp_avg, exp_avg_sq):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    _lib.call("mi_adamw_flat", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), ptr(params_bf16), n,
+              ptr(state), ptr(decay_map), int(unit_base), float(beta1), float(beta2), float(eps), stream_of(params))
+
+
 def cast_bf16_(src, dst):
     if not src.is_cuda:
         dst.copy_(src)
