@@ -3,7 +3,8 @@
 // [B*T][3*H*64] in place -- no head split / merge copies around the kernel.
 //
 // One workgroup (4 waves) per (batch, head); the head's whole K and V (or Q and dO) live in LDS
-// (T <= 256 keys: <= 72 KB), so softmax is exact in one pass (no online rescaling).  Every
+// (T <= 256 keys: <= 72 KB), so softmax is exact in one pass (no online rescaling); longer
+// sequences stream that operand through LDS in slabs (the *_long kernels further down).  Every
 // product is a v_mfma_f32_16x16x32_bf16 in "transposed" form so that an accumulator feeds the
 // next MFMA as its B operand straight from registers:
 //
@@ -575,6 +576,336 @@ __global__ __launch_bounds__(512, 4) void attn_bwd_fused_kernel(const bf16_t* __
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Long sequences (any T >= 1): the three kernels above with the per-wave tile loop turned into a
+// grid dimension and the LDS-resident operand into a loop over slabs of LS rows.
+//
+//   grid (B*H, ceil(T / LB)), 8 waves; wave w owns the 16-row tile LB * blockIdx.y + 16 w and
+//   keeps its fragments and accumulators in registers for the whole kernel
+//   forward / dQ: slabs of K, V rows;  dK/dV: slabs of Q, dO rows plus their LSE and D values
+//
+// Two LDS buffers, one barrier per slab: slab s + 1 is loaded into registers before the barrier
+// that publishes slab s, so its memory latency runs under the MFMAs of slab s, and it is stored to
+// the other buffer after them (every wave has left slab s - 1, the buffer's last reader, once it is
+// past that barrier).  73 KB (dK/dV: 75 KB) of LDS and <= 128 VGPRs: two workgroups per CU.
+// Rows at or past T are staged as zeros (the load itself is clamped to row T - 1, never predicated:
+// no exec-masked branch around it), masked by their global index, and 32-row steps that start at or
+// past T are skipped, so the forward's running max is finite after its first chunk.
+constexpr int LB = 128;               // rows of the owned operand per workgroup (8 waves x 16)
+constexpr int LS = 128;               // rows per LDS slab
+constexpr int LPER = LS * 8 / 512;    // 16-byte pieces per thread, operand and slab
+constexpr int LSLAB = LS * KSTR;      // elements per LDS slab buffer
+
+// plain vector registers (not uint4 structs): selects on them stay in VGPRs
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+struct SlabRegs {
+  u32x4 a[LPER], b[LPER];
+};
+
+__device__ __forceinline__ void slab_load(SlabRegs& r, const bf16_t* src0, size_t ld0, const bf16_t* src1,
+                                          size_t ld1, int row0, int T) {
+#pragma unroll
+  for (int i = 0; i < LPER; ++i) {
+    const int c = threadIdx.x + 512 * i, row = row0 + (c >> 3), part = c & 7;
+    const size_t rc = (size_t)min(row, T - 1);
+    const u32x4 a = *(const u32x4*)(src0 + rc * ld0 + part * 8);
+    const u32x4 b = *(const u32x4*)(src1 + rc * ld1 + part * 8);
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    r.a[i] = row < T ? a : z;
+    r.b[i] = row < T ? b : z;
+  }
+}
+
+__device__ __forceinline__ void slab_store(const SlabRegs& r, bf16_t* dst0, bf16_t* dst1) {
+#pragma unroll
+  for (int i = 0; i < LPER; ++i) {
+    const int c = threadIdx.x + 512 * i, row = c >> 3, part = c & 7;
+    *(u32x4*)&dst0[row * KSTR + part * 8] = r.a[i];
+    *(u32x4*)&dst1[row * KSTR + part * 8] = r.b[i];
+  }
+}
+
+__global__ __launch_bounds__(512, 4) void attn_fwd_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
+                                                              float* __restrict__ lse, int T, int H, float sl2) {
+  constexpr int CP = 2;  // key-tile pairs per online-softmax chunk, as attn_fwd8_kernel
+  static_assert((LS / 32) % CP == 0, "a chunk must not run past its slab");
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * LSLAB];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[2 * LSLAB];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int D = H * HD;
+  const size_t ld = 3 * (size_t)D;
+  const bf16_t* base = qkv + (size_t)b * T * ld + h * HD;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15, q4 = li >> 2, p4 = li & 3;
+  const int qw = blockIdx.y * LB + wv * 16;
+  const bool active = qw < T;  // wave-uniform: a wave whose tile lies past T only stages
+  const int q = qw + li;
+  const bool qv = q < T;
+  bf16x8 qf[2];
+#pragma unroll
+  for (int h2 = 0; h2 < 2; ++h2) qf[h2] = qv ? g16(base + (size_t)q * ld + 32 * h2 + 8 * g) : zero8();
+  float m = -INFINITY, l = 0.f;
+  f32x4 oa[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) oa[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int ns = (T + LS - 1) / LS;
+  SlabRegs r;
+  slab_load(r, base + D, ld, base + 2 * D, ld, 0, T);
+  slab_store(r, Ks, Vs);
+#pragma unroll 1
+  for (int s = 0; s < ns; ++s) {
+    if (s + 1 < ns) slab_load(r, base + D, ld, base + 2 * D, ld, (s + 1) * LS, T);
+    __syncthreads();
+    const bf16_t* K = Ks + (s & 1) * LSLAB;
+    const bf16_t* V = Vs + (s & 1) * LSLAB;
+    const int k0 = s * LS;
+    const int np = active ? min(LS / 32, (T - k0 + 31) >> 5) : 0;  // key-tile pairs that start before T
+#pragma unroll 1
+    for (int c0 = 0; c0 < np; c0 += CP) {
+      f32x4 sc[2 * CP];
+      float cm = -INFINITY;
+#pragma unroll
+      for (int t = 0; t < 2 * CP; ++t) {
+        const int kt = 2 * c0 + t;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2)
+          acc = mfma(*(const bf16x8*)&K[(kt * 16 + li) * KSTR + 32 * h2 + 8 * g], qf[h2], acc);
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          if (k0 + kt * 16 + 4 * g + r4 >= T) acc[r4] = -INFINITY;
+          cm = fmaxf(cm, acc[r4]);
+        }
+        sc[t] = acc;
+      }
+      cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
+      cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
+      const float mn = fmaxf(m, cm);  // finite: the chunk's first key is < T
+      const float alpha = att_exp2((m - mn) * sl2);  // first chunk: exp2(-inf) = 0 (oa, l are 0)
+      m = mn;
+      const float ms = mn * sl2;
+      l *= alpha;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) oa[dt] *= alpha;
+#pragma unroll
+      for (int t = 0; t < 2 * CP; ++t)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const float p = att_exp2(sc[t][r4] * sl2 - ms);
+          sc[t][r4] = p;
+          l += p;
+        }
+#pragma unroll
+      for (int kp = 0; kp < CP; ++kp) {
+        const int ks = c0 + kp;
+        const bf16x8 pb = pack_perm(sc[2 * kp], sc[2 * kp + 1]);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt)
+          oa[dt] = mfma(tr8(V, ks * 32 + 4 * g + q4, ks * 32 + 16 + 4 * g + q4, (dt * 4 + p4) * 4), pb, oa[dt]);
+      }
+    }
+    if (s + 1 < ns) slab_store(r, Ks + ((s + 1) & 1) * LSLAB, Vs + ((s + 1) & 1) * LSLAB);
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  if (qv) {
+    const float inv = 1.f / l;
+    bf16_t* orow = o + ((size_t)b * T + q) * D + h * HD;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) store4bf(orow + dt * 16 + 4 * g, oa[dt], inv);
+    if (g == 0) lse[(size_t)bh * T + q] = (m * sl2 + log2f(l)) * LN2;
+  }
+}
+
+__global__ __launch_bounds__(512, 4) void attn_bwd_dq_long_kernel(const bf16_t* __restrict__ qkv,
+                                                                 const bf16_t* __restrict__ o,
+                                                                 const bf16_t* __restrict__ dout,
+                                                                 const float* __restrict__ lse,
+                                                                 float* __restrict__ dvec, bf16_t* __restrict__ dqkv,
+                                                                 int T, int H, float sl2, float scale) {
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[2 * LSLAB];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[2 * LSLAB];
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int D = H * HD;
+  const size_t ld = 3 * (size_t)D;
+  const bf16_t* base = qkv + (size_t)b * T * ld + h * HD;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15, q4 = li >> 2, p4 = li & 3;
+  const int qw = blockIdx.y * LB + wv * 16;
+  const bool active = qw < T;
+  const int q = qw + li;
+  const bool qv = q < T;
+  const size_t orow = ((size_t)b * T + q) * D + h * HD;
+  const float lse_q = lse[(size_t)bh * T + min(q, T - 1)];
+  bf16x8 qf[2], df[2];
+  float dd = 0.f;
+#pragma unroll
+  for (int h2 = 0; h2 < 2; ++h2) {
+    qf[h2] = qv ? g16(base + (size_t)q * ld + 32 * h2 + 8 * g) : zero8();
+    df[h2] = qv ? g16(dout + orow + 32 * h2 + 8 * g) : zero8();
+    const bf16x8 of = qv ? g16(o + orow + 32 * h2 + 8 * g) : zero8();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) dd += (float)df[h2][j] * (float)of[j];
+  }
+  dd += __shfl_xor(dd, 16, 64);
+  dd += __shfl_xor(dd, 32, 64);
+  const float l2 = qv ? lse_q * LOG2E : 0.f;
+  if (qv && g == 0) dvec[(size_t)bh * T + q] = dd;
+  f32x4 dq[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int ns = (T + LS - 1) / LS;
+  SlabRegs r;
+  slab_load(r, base + D, ld, base + 2 * D, ld, 0, T);
+  slab_store(r, Ks, Vs);
+#pragma unroll 1
+  for (int s = 0; s < ns; ++s) {
+    if (s + 1 < ns) slab_load(r, base + D, ld, base + 2 * D, ld, (s + 1) * LS, T);
+    __syncthreads();
+    const bf16_t* K = Ks + (s & 1) * LSLAB;
+    const bf16_t* V = Vs + (s & 1) * LSLAB;
+    const int k0 = s * LS;
+    const int np = active ? min(LS / 32, (T - k0 + 31) >> 5) : 0;
+#pragma unroll 1
+    for (int ks = 0; ks < np; ++ks) {
+      f32x4 ds[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int kt = 2 * ks + t;
+        f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+          sv = mfma(*(const bf16x8*)&K[(kt * 16 + li) * KSTR + 32 * h2 + 8 * g], qf[h2], sv);
+          dp = mfma(*(const bf16x8*)&V[(kt * 16 + li) * KSTR + 32 * h2 + 8 * g], df[h2], dp);
+        }
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const bool valid = qv && (k0 + kt * 16 + 4 * g + r4 < T);
+          const float e = att_exp2(sv[r4] * sl2 - l2);  // unconditional + select (see attn_bwd_dq_kernel)
+          ds[t][r4] = (valid ? e : 0.f) * (dp[r4] - dd);
+        }
+      }
+      const bf16x8 sb = pack_perm(ds[0], ds[1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+        dq[dt] = mfma(tr8(K, ks * 32 + 4 * g + q4, ks * 32 + 16 + 4 * g + q4, (dt * 4 + p4) * 4), sb, dq[dt]);
+    }
+    if (s + 1 < ns) slab_store(r, Ks + ((s + 1) & 1) * LSLAB, Vs + ((s + 1) & 1) * LSLAB);
+  }
+  if (qv) {
+    bf16_t* drow = dqkv + ((size_t)b * T + q) * ld + h * HD;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) store4bf(drow + dt * 16 + 4 * g, dq[dt], scale);
+  }
+}
+
+// one row's LSE (log2 domain; +inf at or past T: P = 0) and D = rowsum(dO * O) for the dK/dV slabs
+__device__ __forceinline__ void vec_load(float& pl, float& pd, const float* lrow, const float* drow, int row,
+                                         int T) {
+  const int rc = min(row, T - 1);
+  const float a = lrow[rc] * LOG2E, c = drow[rc];
+  pl = row < T ? a : INFINITY;
+  pd = row < T ? c : 0.f;
+}
+
+__global__ __launch_bounds__(512, 4) void attn_bwd_dkv_long_kernel(const bf16_t* __restrict__ qkv,
+                                                                  const bf16_t* __restrict__ dout,
+                                                                  const float* __restrict__ lse,
+                                                                  const float* __restrict__ dvec,
+                                                                  bf16_t* __restrict__ dqkv, int T, int H, float sl2,
+                                                                  float scale) {
+  __shared__ __attribute__((aligned(16))) bf16_t Qs[2 * LSLAB];
+  __shared__ __attribute__((aligned(16))) bf16_t Ds[2 * LSLAB];
+  __shared__ float Ls[2 * LS], Dv[2 * LS];
+  static_assert(LS <= 512, "one thread per staged LSE / D value");
+  const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
+  const int D = H * HD;
+  const size_t ld = 3 * (size_t)D;
+  const bf16_t* base = qkv + (size_t)b * T * ld + h * HD;
+  const bf16_t* dbase = dout + (size_t)b * T * D + h * HD;
+  const float* lrow = lse + (size_t)bh * T;
+  const float* drow_v = dvec + (size_t)bh * T;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int g = lane >> 4, li = lane & 15, q4 = li >> 2, p4 = li & 3;
+  const int kw = blockIdx.y * LB + wv * 16;
+  const bool active = kw < T;
+  const int key = kw + li;
+  const bool kv = key < T;
+  bf16x8 kf[2], vf[2];
+#pragma unroll
+  for (int h2 = 0; h2 < 2; ++h2) {
+    kf[h2] = kv ? g16(base + (size_t)key * ld + D + 32 * h2 + 8 * g) : zero8();
+    vf[h2] = kv ? g16(base + (size_t)key * ld + 2 * D + 32 * h2 + 8 * g) : zero8();
+  }
+  f32x4 dk[4], dv[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = dk[dt]; }
+  const int ns = (T + LS - 1) / LS;
+  const int vt = threadIdx.x & (LS - 1);  // threads >= LS repeat a row: loads stay in bounds, no store
+  SlabRegs r;
+  float pl, pd;
+  slab_load(r, base, ld, dbase, (size_t)D, 0, T);
+  vec_load(pl, pd, lrow, drow_v, vt, T);
+  slab_store(r, Qs, Ds);
+  if (threadIdx.x < LS) { Ls[vt] = pl; Dv[vt] = pd; }
+#pragma unroll 1
+  for (int s = 0; s < ns; ++s) {
+    if (s + 1 < ns) {
+      slab_load(r, base, ld, dbase, (size_t)D, (s + 1) * LS, T);
+      vec_load(pl, pd, lrow, drow_v, (s + 1) * LS + vt, T);
+    }
+    __syncthreads();
+    const bf16_t* Q = Qs + (s & 1) * LSLAB;
+    const bf16_t* DO = Ds + (s & 1) * LSLAB;
+    const float* L = Ls + (s & 1) * LS;
+    const float* DD = Dv + (s & 1) * LS;
+    const int np = active ? min(LS / 32, (T - s * LS + 31) >> 5) : 0;  // query-tile pairs that start before T
+#pragma unroll 1
+    for (int qs = 0; qs < np; ++qs) {
+      f32x4 P[2], S[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int row = (2 * qs + t) * 16 + li;
+        f32x4 sv = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+          sv = mfma(*(const bf16x8*)&Q[row * KSTR + 32 * h2 + 8 * g], kf[h2], sv);
+          dp = mfma(*(const bf16x8*)&DO[row * KSTR + 32 * h2 + 8 * g], vf[h2], dp);
+        }
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const int qq = (2 * qs + t) * 16 + 4 * g + r4;
+          const float e = att_exp2(sv[r4] * sl2 - L[qq]);  // unconditional + select (see attn_bwd_dq_kernel)
+          const float p = kv ? e : 0.f;
+          P[t][r4] = p;
+          S[t][r4] = p * (dp[r4] - DD[qq]);
+        }
+      }
+      const bf16x8 pb = pack_perm(P[0], P[1]), sb = pack_perm(S[0], S[1]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const int r0 = qs * 32 + 4 * g + q4, r1 = r0 + 16, col = (dt * 4 + p4) * 4;
+        dv[dt] = mfma(tr8(DO, r0, r1, col), pb, dv[dt]);
+        dk[dt] = mfma(tr8(Q, r0, r1, col), sb, dk[dt]);
+      }
+    }
+    if (s + 1 < ns) {
+      const int nb = (s + 1) & 1;
+      slab_store(r, Qs + nb * LSLAB, Ds + nb * LSLAB);
+      if (threadIdx.x < LS) { Ls[nb * LS + vt] = pl; Dv[nb * LS + vt] = pd; }
+    }
+  }
+  if (kv) {
+    bf16_t* drow = dqkv + ((size_t)b * T + key) * ld + h * HD;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      store4bf(drow + D + dt * 16 + 4 * g, dk[dt], scale);
+      store4bf(drow + 2 * D + dt * 16 + 4 * g, dv[dt], 1.f);
+    }
+  }
+}
+
 }  // namespace
 
 #define MI_ATT_SWITCH(NK2, LAUNCH)                                                                       \
@@ -704,5 +1035,35 @@ MI_API int mi_attn_bwd(const void* qkv, const void* o, const void* dout, const f
                        (const bf16_t*)dout, lse, dvec, (bf16_t*)dqkv, T, H, sl2, scale, att_rot())
   MI_ATT_SWITCH((T + 31) / 32, L)
 #undef L
+  return (int)hipGetLastError();
+}
+
+// ---- long sequences: the slab-streaming kernels, any 1 <= T <= mi_attn_long_max_seq()
+// The query / key block index is blockIdx.y (at most 65535 blocks of LB rows); every global offset
+// is a size_t, and the int row indices stay below T + LS.
+MI_API int mi_attn_long_max_seq() { return LB * 65535; }
+
+static bool att_long_ok(int B, int T, int H) {
+  return T > 0 && T <= LB * 65535 && B > 0 && H > 0 && (long long)B * H <= 0x7fffffffLL;
+}
+
+MI_API int mi_attn_fwd_long(const void* qkv, void* o, float* lse, int B, int T, int H, float scale,
+                            hipStream_t st) {
+  if (!att_long_ok(B, T, H)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(attn_fwd_long_kernel, dim3(B * H, (T + LB - 1) / LB), dim3(512), 0, st, (const bf16_t*)qkv,
+                     (bf16_t*)o, lse, T, H, scale * LOG2E);
+  return (int)hipGetLastError();
+}
+
+// as mi_attn_bwd; dvec is written by the dQ kernel and read by the dK/dV kernel behind it
+MI_API int mi_attn_bwd_long(const void* qkv, const void* o, const void* dout, const float* lse, float* dvec,
+                            void* dqkv, int B, int T, int H, float scale, hipStream_t st) {
+  if (!att_long_ok(B, T, H)) return (int)hipErrorInvalidValue;
+  const dim3 grid(B * H, (T + LB - 1) / LB);
+  const float sl2 = scale * LOG2E;
+  hipLaunchKernelGGL(attn_bwd_dq_long_kernel, grid, dim3(512), 0, st, (const bf16_t*)qkv, (const bf16_t*)o,
+                     (const bf16_t*)dout, lse, dvec, (bf16_t*)dqkv, T, H, sl2, scale);
+  hipLaunchKernelGGL(attn_bwd_dkv_long_kernel, grid, dim3(512), 0, st, (const bf16_t*)qkv, (const bf16_t*)dout,
+                     lse, (const float*)dvec, (bf16_t*)dqkv, T, H, sl2, scale);
   return (int)hipGetLastError();
 }

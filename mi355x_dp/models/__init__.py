@@ -9,6 +9,12 @@ _REGISTRY = {
 }
 
 
+def interpolate_embeddings(image_size, patch_size, model_state, interpolation_mode="bicubic"):
+    """ViT position-embedding resize for another input resolution (see ``models.vit``)."""
+    from .vit import interpolate_embeddings as _f
+    return _f(image_size, patch_size, model_state, interpolation_mode)
+
+
 def get_model(name: str, **kw):
     name = name.lower().replace("-", "").replace("_", "")
     if name == "vitb16":

@@ -171,6 +171,30 @@ class VisionTransformer(nn.Module):
         return self.heads(x[:, 0])
 
 
+def interpolate_embeddings(image_size, patch_size, model_state, interpolation_mode="bicubic"):
+    """Resize ``encoder.pos_embedding`` of a ViT state dict to another input resolution (fine-tuning
+    at 384² from 224² weights: [1, 197, D] -> [1, 577, D]), as torchvision's function of this name:
+    the class-token row is kept, the g x g grid of patch rows is resized as a [1, D, g, g] image with
+    ``F.interpolate(..., align_corners=True)``.  Returns a new state dict; ``model_state`` and its
+    tensors are left as they are."""
+    pos = model_state["encoder.pos_embedding"]
+    n, seq, dim = pos.shape
+    if n != 1:
+        raise ValueError(f"unexpected position embedding shape {tuple(pos.shape)}")
+    out = OrderedDict(model_state)
+    g_new = image_size // patch_size
+    if g_new * g_new + 1 == seq:
+        return out
+    g_old = math.isqrt(seq - 1)
+    if g_old * g_old != seq - 1:
+        raise ValueError(f"position embedding of {seq - 1} patch tokens is not a square grid")
+    grid = pos[:, 1:].permute(0, 2, 1).reshape(1, dim, g_old, g_old)
+    grid = F.interpolate(grid.float(), size=(g_new, g_new), mode=interpolation_mode, align_corners=True)
+    grid = grid.reshape(1, dim, g_new * g_new).permute(0, 2, 1).to(pos.dtype)
+    out["encoder.pos_embedding"] = torch.cat([pos[:, :1], grid], dim=1)
+    return out
+
+
 def vit_b_16(num_classes=1000, image_size=224, **kw):
     return VisionTransformer(image_size=image_size, patch_size=16, num_layers=12, num_heads=12, hidden_dim=768,
                              mlp_dim=3072, num_classes=num_classes, **kw)

@@ -112,36 +112,57 @@ def _dgrad(dy2, weight, epi=EPI_NONE, aux=None):
 
 
 # ------------------------------------------------------------------ attention
+ATT_RESIDENT_MAX = 256  # mi_attn_fwd / mi_attn_bwd: the head's whole K, V (Q, dO) in LDS
+_ATT_LONG_MAX = []
+
+
+def _att_long_max():
+    """Longest sequence of the slab-streaming kernels (mi_attn_fwd_long / mi_attn_bwd_long).
+    MI355X_DP_ATT_LONG=0 (read at call time, for A/B runs) switches them off: T > 256 then takes the
+    SDPA fallback as it did before they existed."""
+    if _os.environ.get("MI355X_DP_ATT_LONG", "1") == "0":
+        return ATT_RESIDENT_MAX
+    if not _ATT_LONG_MAX:
+        _ATT_LONG_MAX.append(int(_lib.load().mi_attn_long_max_seq()))
+    return _ATT_LONG_MAX[0]
+
+
 def native_attention_ok(T, head_dim):
-    return head_dim == 64 and 0 < T <= 256
+    if head_dim != 64 or T <= 0:
+        return False
+    return T <= ATT_RESIDENT_MAX or T <= _att_long_max()
 
 
 _SDPA_WARNED = set()
 
 
 def _warn_sdpa(T, Dh):
-    """The native kernel covers head dim 64 with T <= 256 (ViT-B/16); anything else runs torch's
-    scaled_dot_product_attention -- said once per shape, so a non-native path is never silent.
-    MI355X_DP_STRICT_NATIVE=1 makes it an error instead."""
+    """The native kernels cover head dim 64 at any sequence length the long kernels take (T <= 256:
+    operands resident in LDS, ViT-B/16 at 224²; above: streamed in slabs, e.g. 577 tokens at 384²);
+    anything else runs torch's scaled_dot_product_attention -- said once per shape, so a non-native
+    path is never silent.  MI355X_DP_STRICT_NATIVE=1 makes it an error instead."""
     if _os.environ.get("MI355X_DP_STRICT_NATIVE", "0") == "1":
         raise RuntimeError(f"attention: no native kernel for T={T}, head_dim={Dh} (MI355X_DP_STRICT_NATIVE=1)")
     if (T, Dh) not in _SDPA_WARNED:
         _SDPA_WARNED.add((T, Dh))
         import warnings
-        warnings.warn(f"mi355x_dp attention: T={T}, head_dim={Dh} is outside the native kernel "
-                      f"(head_dim 64, T <= 256); using torch scaled_dot_product_attention", stacklevel=3)
+        warnings.warn(f"mi355x_dp attention: T={T}, head_dim={Dh} is outside the native kernels "
+                      f"(head_dim 64, T <= {_att_long_max()}; MI355X_DP_ATT_LONG=0 keeps T <= 256); using torch "
+                      f"scaled_dot_product_attention", stacklevel=3)
 
 
 def _attn_fwd(qkv2, B, T, H, need_grad):
     """softmax(q kᵀ/√d) v over the packed [B·T][3·H·Dh] projection; returns o [B·T][H·Dh].
-    Native kernel (csrc/kernels/attention.hip) for Dh = 64, T <= 256 (ViT-B/16: T = 197)."""
+    Native kernels (csrc/kernels/attention.hip) for Dh = 64: T <= 256 on the resident-operand
+    kernels (ViT-B/16 at 224²: T = 197), longer sequences on the slab-streaming pair."""
     D3 = qkv2.shape[1]
     Dh = D3 // (3 * H)
     scale = 1.0 / (Dh ** 0.5)
     if native_attention_ok(T, Dh):
         o = torch.empty((B * T, H * Dh), dtype=BF16, device=qkv2.device)
         lse = torch.empty((B * H * T,), dtype=F32, device=qkv2.device)
-        _lib.call("mi_attn_fwd", ptr(qkv2), ptr(o), ptr(lse), B, T, H, float(scale), stream_of(qkv2))
+        fn = "mi_attn_fwd" if T <= ATT_RESIDENT_MAX else "mi_attn_fwd_long"
+        _lib.call(fn, ptr(qkv2), ptr(o), ptr(lse), B, T, H, float(scale), stream_of(qkv2))
         return o, (("native", lse, o) if need_grad else None)
     _warn_sdpa(T, Dh)
     if not need_grad:
@@ -161,7 +182,8 @@ def _attn_bwd(state, qkv2, do2, B, T, H):
         _, lse, o = state
         dqkv = torch.empty_like(qkv2)
         dvec = torch.empty((B * H * T,), dtype=F32, device=qkv2.device)
-        _lib.call("mi_attn_bwd", ptr(qkv2), ptr(o), ptr(do2), ptr(lse), ptr(dvec), ptr(dqkv), B, T, H,
+        fn = "mi_attn_bwd" if T <= ATT_RESIDENT_MAX else "mi_attn_bwd_long"
+        _lib.call(fn, ptr(qkv2), ptr(o), ptr(do2), ptr(lse), ptr(dvec), ptr(dqkv), B, T, H,
                   float(1.0 / (Dh ** 0.5)), stream_of(qkv2))
         return dqkv
     _, leaf, o4 = state
