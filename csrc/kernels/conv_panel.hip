@@ -662,10 +662,6 @@ MI_API int mi_panel_conv(const void* x, const void* w, void* y, float* stats, in
   a.fQ = make_fastdiv((uint32_t)Q);
   return launch_plan<0>(p, a, st, tap3 ? "fwd3x3" : "fwd");
 }
-MI_API int mi_panel_conv1x1(const void* x, const void* w, void* y, float* stats, int Nb, int H, int W, int C, int K,
-                            int stride, int P, int Q, hipStream_t st) {
-  return mi_panel_conv(x, w, y, stats, Nb, H, W, C, K, 1, stride, 0, P, Q, st);
-}
 
 // 1x1 or 3x3 (pad 1) / stride-1 conv data gradient on the panel kernel: dy NHWC [Nb,H,W,K], wt [C][R][R][K], dx NHWC
 // [Nb,H,W,C] with nt_kernel's epilogues (PanelArgs::epi; mbits or aux = the BN output for the ReLU

@@ -988,36 +988,12 @@ MI_API int mi_gemm256_tn(const void* A, const void* B, float* C, int M, int N, i
 // rows = output pixels [Nb,P,Q], B = w [N][R][S][Cs]; mode 2 = stride-1 data gradient:
 // gathered = dy [Nb,H,W,Cs] (H,W = the forward output grid, Cs = forward K), rows = dx pixels
 // [Nb,P,Q], B = wt [N][R][S][Cs].  Cs % 64 == 0.  stats: [mi_g256_stat_rows(M, N, K)][2][N] partials
-// (forward: sum / sum of squares; epi 4: BN-backward sums).  C bf16 [M][N].
-MI_API int mi_gemm256_conv2(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
-                            const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs, int P,
-                            int Q, int R, int S, int stride, int pad, int N, int aux_even, hipStream_t st);
-
+// (forward: sum / sum of squares; epi 4: BN-backward sums).  C bf16 [M][N].  aux_even: see G256Args;
+// mbits: the epi 4 / 5 ReLU mask as bytes (see G256Args).
 MI_API int mi_gemm256_conv(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
                            const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs, int P,
-                           int Q, int R, int S, int stride, int pad, int N, hipStream_t st) {
-  return mi_gemm256_conv2(mode, A, B, C, stats, epi, aux, aux2, mean, bn_relu, Nb, H, W, Cs, P, Q, R, S, stride, pad,
-                          N, 0, st);
-}
-
-MI_API int mi_gemm256_conv3(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
-                            const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs, int P,
-                            int Q, int R, int S, int stride, int pad, int N, int aux_even, const void* mbits,
-                            hipStream_t st);
-
-// as mi_gemm256_conv; aux_even: see G256Args
-MI_API int mi_gemm256_conv2(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
-                            const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs, int P,
-                            int Q, int R, int S, int stride, int pad, int N, int aux_even, hipStream_t st) {
-  return mi_gemm256_conv3(mode, A, B, C, stats, epi, aux, aux2, mean, bn_relu, Nb, H, W, Cs, P, Q, R, S, stride, pad,
-                          N, aux_even, nullptr, st);
-}
-
-// as mi_gemm256_conv2; mbits: the epi 4 / 5 ReLU mask as bytes (see G256Args)
-MI_API int mi_gemm256_conv3(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
-                            const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs, int P,
-                            int Q, int R, int S, int stride, int pad, int N, int aux_even, const void* mbits,
-                            hipStream_t st) {
+                           int Q, int R, int S, int stride, int pad, int N, int aux_even, const void* mbits,
+                           hipStream_t st) {
   if ((mode != 1 && mode != 2) || Cs % 64 != 0 || N % 8 != 0 || (mode == 2 && stride != 1) ||
       !(epi == 0 || epi == 3 || epi == 4 || epi == 5) || (epi == 3 && !aux) ||
       (epi >= 4 && bn_relu && !aux && !mbits) || (mbits && (epi < 4 || !bn_relu)) ||
@@ -1079,7 +1055,7 @@ __global__ __launch_bounds__(256) void fbb_wprep_kernel(const bf16_t* __restrict
 }
 
 // dz / c NHWC [Nb,H,W,K], wt bf16 [C][K] (the dgrad weight layout), wq: C * 2K bf16 and bias: C
-// floats of workspace; epilogue / statistics as mi_gemm256_conv3 mode 2 (stats rows:
+// floats of workspace; epilogue / statistics as mi_gemm256_conv mode 2 (stats rows:
 // mi_g256_stat_rows(M, C, 2K)).
 MI_API int mi_gemm256_dgrad_fbb(const void* dz, const void* c, const float* coef, const void* wt, void* wq, float* bias,
                                 void* dx, float* stats, int epi, void* aux, const void* aux2, const float* mean,

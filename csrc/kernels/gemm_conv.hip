@@ -24,6 +24,7 @@
 #include "epilogue.h"
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cstdio>
 #include <vector>
 #include <mutex>
@@ -1445,28 +1446,181 @@ hipError_t launch_nt(NTArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// tile choice shared with the host-side stats-slab sizing (mi_nt_tile_m)
+// NT tile choice: for plain GEMMs (dispatch_nt) and, through nt_route, for every conv route
 int nt_choice(int M, int N) {
   if (N <= 64) return 1;                                         // 128x64
   if ((int64_t)cdiv(M, 128) * cdiv(N, 128) < 512) return 2;     // 64x64 (fill 256 CUs)
   return 0;                                                      // 128x128
 }
 
+// The switches of the conv / GEMM routing, read from the environment once (first use) and
+// overridden by the mi_set_* functions below (tests, A/B runs).
+struct Switches {
+  int gemm256;            // MI355X_DP_GEMM256 (1): the 256x256 kernels (gemm256.hip), GEMMs and convs
+  int conv256_min_tiles;  // MI355X_DP_CONV256_MIN_TILES (96): 256x256 output tiles a conv needs for them
+  int conv256_min_k;      // MI355X_DP_CONV256_MIN_K (512): and its GEMM depth R*S*Cs
+  int panel_first;        // MI355X_DP_PANEL_FIRST (0): 1x1 convs the panel kernel takes leave the 256-wide one
+  int ds256;              // MI355X_DP_DS256 (1): stride-2 1x1 shortcut data gradients as a 256-wide scatter GEMM
+  int halo;               // MI355X_DP_HALO (1): halo tiling of the 3x3 / stride-1 / pad-1 convs
+  int stem;               // MI355X_DP_STEM_KERNEL (1): the 7x7/2 stem kernel (stem_conv.hip)
+  int wgrad256;           // MI355X_DP_WGRAD256 (0 = never): see use_wgrad256
+  int tn256_min_tiles;    // MI355X_DP_TN256_MIN_TILES (128): see use_gemm256_tn
+};
+static Switches& sw() {
+  static Switches s = [] {
+    const auto off = [](const char* name) { const char* e = std::getenv(name); return (e && e[0] == '0') ? 0 : 1; };
+    const auto num = [](const char* name, int dflt, int lo) {
+      const char* e = std::getenv(name);
+      return e ? std::max(lo, std::atoi(e)) : dflt;
+    };
+    Switches v;
+    v.gemm256 = off("MI355X_DP_GEMM256");
+    v.conv256_min_tiles = num("MI355X_DP_CONV256_MIN_TILES", 96, INT_MIN);
+    v.conv256_min_k = num("MI355X_DP_CONV256_MIN_K", 512, INT_MIN);
+    const char* pf = std::getenv("MI355X_DP_PANEL_FIRST");
+    v.panel_first = (pf && pf[0] == '1') ? 1 : 0;
+    v.ds256 = off("MI355X_DP_DS256");
+    v.halo = off("MI355X_DP_HALO");
+    v.stem = off("MI355X_DP_STEM_KERNEL");
+    v.wgrad256 = num("MI355X_DP_WGRAD256", 0, 0);
+    v.tn256_min_tiles = num("MI355X_DP_TN256_MIN_TILES", 128, 1);
+    return v;
+  }();
+  return s;
+}
+
 // Halo tiling (see nt_kernel) for a 3x3 / stride-1 / pad-1 conv whose row grid is P x Q (gathered
 // tensor the same size), Cs channels: rows per tile, or 0 when it does not apply (rows of >= 75 %
 // of a 128-row tile, halo within HALO_PX; 64x64-tile shapes keep the gather path).
 // MI355X_DP_HALO=0 disables.
-static int g_halo = -1;
 static int halo_rp(int M, int N, int R, int S, int stride, int pad, int Cs, int H, int W, int P, int Q) {
-  if (g_halo < 0) {
-    const char* e = std::getenv("MI355X_DP_HALO");
-    g_halo = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!g_halo || R != 3 || S != 3 || stride != 1 || pad != 1 || Cs % 64 != 0 || H != P || W != Q) return 0;
+  if (!sw().halo || R != 3 || S != 3 || stride != 1 || pad != 1 || Cs % 64 != 0 || H != P || W != Q || Q < 1)
+    return 0;
   if (nt_choice(M, N) == 2) return 0;
   const int rp = std::min(128 / Q, P);
   if (rp < 1 || rp * Q * 4 < 128 * 3 || (rp + 2) * (Q + 2) > HALO_PX) return 0;
   return rp;
+}
+
+}  // namespace
+
+// row / eligibility queries of the kernels in the other files a conv can route to
+extern "C" int mi_g256_stat_rows(int M, int N, int K);  // gemm256.hip: 2 per 224- or 256-row tile
+extern "C" int mi_panel_3x3();                          // conv_panel.hip: the 3x3 panel mode is on
+extern "C" int mi_panel_stat_rows2(int M, int N, int K, int dgrad);  // 0: the panel kernel does not take it
+extern "C" int mi_panel_fbb_rows(int M, int C, int K);
+extern "C" int mi_stem_conv_ok(int C, int K, int R, int S, int stride, int pad, int Q);  // stem_conv.hip
+extern "C" int mi_stem_conv_stat_rows(int Nb, int P);
+
+namespace {
+
+// ---- conv routing: which kernel a forward / data-gradient conv runs on and how many statistics-slab
+// rows that kernel writes.  The launches (mi_conv2d_fwd, mi_conv2d_dgrad_ex4, the folded data
+// gradient) and the size queries Python allocates the slabs from all read the same ConvRoute: the
+// order of precedence and the eligibility conditions are written here and nowhere else.
+enum class ConvKernel { None, Stem, G256, G256Scatter, Panel, NtHalo, Nt, NtClasses };
+struct ConvRoute {
+  ConvKernel k;
+  int stat_rows;  // rows of the statistics slab the kernel writes
+  int bm, bn;     // the NT kinds: tile
+  int halo_rp;    // NtHalo: output rows per tile
+};
+
+// stem_conv.hip: persistent LDS-ring kernel for the 7x7/2 stem on 8-channel input (forward and
+// weight gradient)
+static bool use_stem_kernel(int C, int K, int R, int S, int stride, int pad, int Q) {
+  return sw().stem && mi_stem_conv_ok(C, K, R, S, stride, pad, Q);
+}
+
+// Convolutions with >= 256 output channels and enough 256x256 tiles run on the deep-pipelined
+// kernel (gemm256.hip): forward and stride-1 data gradient.  M x N outputs, Cs gathered channels,
+// GEMM depth Kt = R*S*Cs.
+static bool conv256_ok(int M, int N, int Cs, int Kt) {
+  const Switches& s = sw();
+  // depth below conv256_min_k stays on the 128-tile kernel: a 1x1 conv over few channels is one or
+  // two k-tiles -- nothing for the 256x256 pipeline to overlap, and its 128 KB of LDS holds the CU
+  // to one block through a load-latency-bound prologue / epilogue
+  if (!(s.gemm256 && Cs % 64 == 0 && Kt >= s.conv256_min_k && N % 8 == 0 && N >= 256 &&
+        (int64_t)cdiv(M, 256) * cdiv(N, 256) >= s.conv256_min_tiles))
+    return false;
+  // panel_first: a 1x1 conv the panel kernel takes (K up to 1024 with 32-column panels) leaves the
+  // 256-wide kernel (forward and stride-1 data gradient alike: the panel plan does not depend on
+  // the direction)
+  return !(s.panel_first && Kt == Cs && mi_panel_stat_rows2(M, N, Kt, 0) > 0);
+}
+
+// statistics rows of the panel kernel (conv_panel.hip) where it takes the conv, else 0: forward 1x1
+// (pad 0, any stride) and, in the 3x3 panel mode, 3x3 / stride 1 / pad 1
+static int panel_fwd_rows(int M, int N, int C, int R, int S, int stride, int pad, int H, int W, int P, int Q) {
+  if (C % 64 != 0) return 0;
+  if (R == 3 && S == 3 && stride == 1 && pad == 1 && P == H && Q == W)
+    return mi_panel_3x3() ? mi_panel_stat_rows2(M, N, 9 * C, 0) : 0;
+  if (R != 1 || S != 1 || pad != 0 || P != (H - 1) / stride + 1 || Q != (W - 1) / stride + 1) return 0;
+  return mi_panel_stat_rows2(M, N, C, 0);
+}
+// the stride-1 data gradient of the same convs
+static int panel_dgrad_rows(int M, int C, int K, int R, int S, int stride, int pad) {
+  if (stride != 1 || K % 64 != 0 || R != S || !(R == 1 || (R == 3 && mi_panel_3x3())) || pad != R / 2) return 0;
+  return mi_panel_stat_rows2(M, C, R * S * K, 1);
+}
+
+// the 128-tile NT kernels: M x N outputs; rp > 0: halo tiles of rp of an image's P output rows
+static ConvRoute nt_route(int M, int N, int rp = 0, int Nb = 0, int P = 0) {
+  const int c = nt_choice(M, N);
+  const int bm = c == 2 ? 64 : 128, bn = c == 0 ? 128 : 64;
+  if (rp > 0) return {ConvKernel::NtHalo, Nb * cdiv(P, rp), bm, bn, rp};
+  return {ConvKernel::Nt, cdiv(M, bm), bm, bn, 0};
+}
+
+// Conv forward, x [Nb,H,W,C] -> y [Nb,P,Q,K].  nt_only: the caller's epilogue (fp32 output, bias)
+// exists on the 128-tile kernels alone.
+static ConvRoute route_fwd(int Nb, int H, int W, int C, int K, int R, int S, int stride, int pad, int P, int Q,
+                           bool nt_only = false) {
+  const int M = Nb * P * Q, Kt = R * S * C;
+  if (!nt_only) {
+    if (use_stem_kernel(C, K, R, S, stride, pad, Q))
+      return {ConvKernel::Stem, mi_stem_conv_stat_rows(Nb, P), 0, 0, 0};
+    if (conv256_ok(M, K, C, Kt)) return {ConvKernel::G256, mi_g256_stat_rows(M, K, Kt), 0, 0, 0};
+    if (const int pr = panel_fwd_rows(M, K, C, R, S, stride, pad, H, W, P, Q); pr > 0)
+      return {ConvKernel::Panel, pr, 0, 0, 0};
+  }
+  return nt_route(M, K, halo_rp(M, K, R, S, stride, pad, C, H, W, P, Q), Nb, P);
+}
+
+// Conv data gradient, dy [Nb,P,Q,K] -> dx [Nb,H,W,C], with mi_conv2d_dgrad_ex4's epi and flags (the
+// size queries ask for epi 4, flags 0: only the epilogues with statistics have a slab).
+static ConvRoute route_dgrad(int Nb, int H, int W, int C, int K, int R, int S, int stride, int pad, int P, int Q,
+                             int epi, int flags) {
+  const int M = Nb * H * W, Kt = R * S * K;
+  if (stride == 1 && conv256_ok(M, C, K, Kt)) return {ConvKernel::G256, mi_g256_stat_rows(M, C, Kt), 0, 0, 0};
+  // the stride-2 1x1 data gradient of a projection shortcut (only the even pixels, flags bit 0) as a
+  // plain GEMM over dy's pixels on the 256-wide kernel, rows scattered to the even pixels of dx
+  if (stride == 2 && R == 1 && S == 1 && pad == 0 && epi == 0 && (flags & 1) && H == 2 * P && W == 2 * Q &&
+      sw().ds256 && conv256_ok(Nb * P * Q, C, K, K))
+    return {ConvKernel::G256Scatter, 0, 0, 0, 0};
+  if (const int pr = panel_dgrad_rows(M, C, K, R, S, stride, pad); pr > 0) return {ConvKernel::Panel, pr, 0, 0, 0};
+  if (stride != 1) {
+    // parity-class decomposition (one class per blockIdx.y): every class is tiled like the largest
+    ConvRoute r = nt_route(M, C);
+    int mrows = 0;
+    for (int c = 0; c < 4; ++c) mrows = std::max(mrows, Nb * ((H - c / 2 + 1) / 2) * ((W - c % 2 + 1) / 2));
+    r.k = ConvKernel::NtClasses;
+    r.stat_rows = 4 * cdiv(mrows, r.bm);
+    return r;
+  }
+  // gathered tensor = dy (spatial P,Q, channels K); rows = dx pixels (H, W)
+  return nt_route(M, C, halo_rp(M, C, R, S, stride, pad, K, P, Q, H, W), Nb, H);
+}
+
+// Folded BatchNorm backward, the 1x1 / stride-1 data gradient over [dz | c] (2K deep): the panel
+// kernel when the doubled depth fits its LDS (conv_panel.hip), else the 256-wide kernel where the
+// unfolded data gradient runs there (gemm256.hip mi_gemm256_dgrad_fbb); None: not eligible (the
+// caller materialises dX)
+static ConvRoute route_dgrad_fold(int M, int C, int K) {
+  if (K % 64 != 0 || C % 64 != 0) return {ConvKernel::None, 0, 0, 0, 0};
+  if (const int pr = mi_panel_fbb_rows(M, C, K); pr > 0) return {ConvKernel::Panel, pr, 0, 0, 0};
+  if (conv256_ok(M, C, K, K)) return {ConvKernel::G256, mi_g256_stat_rows(M, C, 2 * K), 0, 0, 0};
+  return {ConvKernel::None, 0, 0, 0, 0};
 }
 
 // MI355X_DP_TRACE_GEMM=1: print every distinct GEMM / conv dispatch (kernel, geometry, epilogue) once
@@ -1488,33 +1642,25 @@ static void trace_gemm(const char* what, int mode, int M, int N, int K, int Cs, 
           mode, M, N, K, Cs, R, stride, epi, stats, blocks, splits);
 }
 
-hipError_t dispatch_nt(NTArgs& a, hipStream_t st) {
-  if (a.mode == 1 || a.mode == 2) {
-    const ConvGeom& g = a.g;
-    const int rp = halo_rp(a.M, a.N, g.R, g.S, g.stride, g.pad, g.Cs, g.H, g.W, g.P, g.Q);
-    if (rp > 0) {
-      a.halo_rp = rp;
-      a.halo_pb = cdiv(g.P, rp);
-      a.fPB = make_fastdiv((uint32_t)a.halo_pb);
-      a.fHW2 = make_fastdiv((uint32_t)(g.Q + 2));
-      trace_gemm(nt_choice(a.M, a.N) == 1 ? "nt128x64-halo" : "nt128x128-halo", a.mode, a.M, a.N, a.K, g.Cs, g.R,
-                 g.stride, a.epi, a.stats != nullptr, (a.M / (g.P * g.Q)) * a.halo_pb, 1);
-      return nt_choice(a.M, a.N) == 1 ? launch_nt<128, 64>(a, st) : launch_nt<128, 128>(a, st);
-    }
+// launch the NT kernel an NT route names (tile, halo tiling)
+hipError_t dispatch_nt(NTArgs& a, hipStream_t st, const ConvRoute& r) {
+  const ConvGeom& g = a.g;
+  if (r.k == ConvKernel::NtHalo) {
+    a.halo_rp = r.halo_rp;
+    a.halo_pb = cdiv(g.P, r.halo_rp);
+    a.fPB = make_fastdiv((uint32_t)a.halo_pb);
+    a.fHW2 = make_fastdiv((uint32_t)(g.Q + 2));
+    trace_gemm(r.bn == 64 ? "nt128x64-halo" : "nt128x128-halo", a.mode, a.M, a.N, a.K, g.Cs, g.R, g.stride, a.epi,
+               a.stats != nullptr, (a.M / (g.P * g.Q)) * a.halo_pb, 1);
+  } else {
+    trace_gemm(r.bm == 64 ? "nt64x64" : (r.bn == 64 ? "nt128x64" : "nt128x128"), a.mode, a.M, a.N, a.K, g.Cs, g.R,
+               g.stride, a.epi, a.stats != nullptr, cdiv(a.M, r.bm) * cdiv(a.N, r.bn), a.mode == 3 ? a.ncls : 1);
   }
-  {
-    static const char* names[3] = {"nt128x128", "nt128x64", "nt64x64"};
-    const int c = nt_choice(a.M, a.N);
-    const int bm = c == 2 ? 64 : 128, bn = c == 0 ? 128 : 64;
-    trace_gemm(names[c], a.mode, a.M, a.N, a.K, a.g.Cs, a.g.R, a.g.stride, a.epi, a.stats != nullptr,
-               cdiv(a.M, bm) * cdiv(a.N, bn), a.mode == 3 ? a.ncls : 1);
-  }
-  switch (nt_choice(a.M, a.N)) {
-    case 1: return launch_nt<128, 64>(a, st);
-    case 2: return launch_nt<64, 64>(a, st);
-    default: return launch_nt<128, 128>(a, st);
-  }
+  if (r.bm == 64) return launch_nt<64, 64>(a, st);
+  return r.bn == 64 ? launch_nt<128, 64>(a, st) : launch_nt<128, 128>(a, st);
 }
+// plain GEMM (mode 0)
+hipError_t dispatch_nt(NTArgs& a, hipStream_t st) { return dispatch_nt(a, st, nt_route(a.M, a.N)); }
 
 // Split-K slab workspace of the TN kernels (fp32, grown on demand and reused in stream order).  One
 // per device for every stream, plus one for the device's registered weight-gradient side stream
@@ -1743,143 +1889,71 @@ MI_API int mi_set_nt_stages(int stages) {
   return 0;
 }
 
-// Convolutions with >= 256 output channels and enough 256x256 tiles run on the deep-pipelined
-// kernel (gemm256.hip): forward and stride-1 data gradient (MI355X_DP_GEMM256=0 disables;
-// MI355X_DP_CONV256_MIN_TILES sets the minimum tile count, default 96).
-extern "C" int mi_gemm256_conv2(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
-                                const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs,
-                                int P, int Q, int R, int S, int stride, int pad, int N, int aux_even, hipStream_t st);
+// ---- the routing switches (Switches, above)
+MI_API void mi_set_panel_first(int on) { sw().panel_first = on ? 1 : 0; }
+MI_API void mi_set_conv256_min_tiles(int t) { sw().conv256_min_tiles = t; }
+// minimum GEMM depth R*S*Cs for the 256x256 conv path (tests force small shapes onto it with 0)
+MI_API void mi_set_conv256_min_k(int k) { sw().conv256_min_k = k; }
+MI_API void mi_set_ds256(int on) { sw().ds256 = on ? 1 : 0; }
+MI_API void mi_set_wgrad256(int min_tiles) { sw().wgrad256 = std::max(0, min_tiles); }
+// MI355X_DP_GEMM256 is one switch: off, the convs leave the 256x256 kernels too (this setter used to
+// reach only the plain GEMMs and left the conv path, which it documented, on)
+MI_API void mi_set_gemm256(int on) { sw().gemm256 = on ? 1 : 0; }
+
+// the kernels of the other files the routes name
 extern "C" int mi_gemm256_conv(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
                                const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs,
-                               int P, int Q, int R, int S, int stride, int pad, int N, hipStream_t st);
-static int g_gemm256_env = -1, g_conv256_min_tiles = -1, g_conv256_min_k = 64;
-extern "C" int mi_g256_stat_rows(int M, int N, int K);  // gemm256.hip: 2 per 224- or 256-row tile
-extern "C" int mi_panel_stat_rows(int M, int N, int K);
-static int g_panel_first = -1;
-static bool use_gemm256_conv(int M, int N, int Cs, int Kt) {
-  if (g_gemm256_env < 0) {
-    const char* e = std::getenv("MI355X_DP_GEMM256");
-    g_gemm256_env = (e && e[0] == '0') ? 0 : 1;
-    const char* t = std::getenv("MI355X_DP_CONV256_MIN_TILES");
-    g_conv256_min_tiles = t ? std::atoi(t) : 96;
-    // GEMM depth (R*S*Cs) below which a conv stays on the 128-tile kernel: a 1x1 conv over few
-    // channels is one or two k-tiles -- nothing for the 256x256 pipeline to overlap, and its 128 KB
-    // of LDS holds the CU to one block through a load-latency-bound prologue / epilogue
-    const char* c = std::getenv("MI355X_DP_CONV256_MIN_K");
-    g_conv256_min_k = c ? std::atoi(c) : 512;
-  }
-  if (!(g_gemm256_env && Cs % 64 == 0 && Kt >= g_conv256_min_k && N % 8 == 0 && N >= 256 &&
-        (int64_t)cdiv(M, 256) * cdiv(N, 256) >= g_conv256_min_tiles))
-    return false;
-  // MI355X_DP_PANEL_FIRST=1: a 1x1 conv the panel kernel takes (K up to 1024 with 32-column panels)
-  // leaves the 256-wide kernel (forward and stride-1 data gradient alike: the panel plan does not
-  // depend on the direction)
-  if (g_panel_first < 0) {
-    const char* e = std::getenv("MI355X_DP_PANEL_FIRST");
-    g_panel_first = (e && e[0] == '1') ? 1 : 0;
-  }
-  if (g_panel_first && Kt == Cs && mi_panel_stat_rows(M, N, Kt) > 0) return false;
-  return true;
-}
-
-MI_API void mi_set_panel_first(int on) {
-  use_gemm256_conv(0, 0, 0, 0);  // env init
-  g_panel_first = on ? 1 : 0;
-}
-
-MI_API void mi_set_conv256_min_tiles(int t) {
-  use_gemm256_conv(0, 0, 0, 0);  // env init
-  g_conv256_min_tiles = t;
-}
-
-// minimum GEMM depth R*S*Cs for the 256x256 conv path (tests force small shapes onto it with 0)
-MI_API void mi_set_conv256_min_k(int k) {
-  use_gemm256_conv(0, 0, 0, 0);  // env init
-  g_conv256_min_k = k;
-}
-
-// conv_panel.hip: persistent resident-weight kernel for the short-K 1x1 convolutions (forward)
-extern "C" int mi_panel_stat_rows(int M, int N, int K);
-extern "C" int mi_panel_stat_rows2(int M, int N, int K, int dgrad);
+                               int P, int Q, int R, int S, int stride, int pad, int N, int aux_even,
+                               const void* mbits, hipStream_t st);
+extern "C" int mi_gemm256_nt_scat2(const void* A, const void* B, void* C, int M, int N, int K, int Q, int W,
+                                   hipStream_t st);
+extern "C" int mi_panel_conv(const void* x, const void* w, void* y, float* stats, int Nb, int H, int W, int C, int K,
+                             int R, int stride, int pad, int P, int Q, hipStream_t st);
 extern "C" int mi_panel_dgrad(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
                               int epi, const void* aux, const void* aux2, const float* mean, int bn_relu, float* stats,
                               int aux_even, const void* mbits, const void* acc_src, hipStream_t st);
-extern "C" int mi_panel_conv(const void* x, const void* w, void* y, float* stats, int Nb, int H, int W, int C, int K,
-                             int R, int stride, int pad, int P, int Q, hipStream_t st);
-// a 1x1 or 3x3 (pad 1) stride-1 data gradient runs on the panel kernel (the statistics slab rows it
-// writes), else 0
-extern "C" int mi_panel_3x3();
-static int panel_rows_dgrad(int M, int C, int K, int RS, int stride) {
-  if ((RS != 1 && !(RS == 9 && mi_panel_3x3())) || stride != 1 || K % 64 != 0) return 0;
-  return mi_panel_stat_rows2(M, C, RS * K, 1);
-}
-extern "C" int mi_panel_conv1x1(const void* x, const void* w, void* y, float* stats, int Nb, int H, int W, int C,
-                                int K, int stride, int P, int Q, hipStream_t st);
-static int panel_rows_fwd(int M, int N, int C, int R, int S, int pad, int H, int W, int P, int Q, int stride) {
-  if (C % 64 != 0) return 0;
-  if (R == 3 && S == 3 && stride == 1 && pad == 1 && P == H && Q == W)
-    return mi_panel_3x3() ? mi_panel_stat_rows(M, N, 9 * C) : 0;
-  if (R != 1 || S != 1 || pad != 0 || P != (H - 1) / stride + 1 || Q != (W - 1) / stride + 1) return 0;
-  return mi_panel_stat_rows(M, N, C);
-}
-
-// stem_conv.hip: persistent LDS-ring kernel for the 7x7/2 stem on 8-channel input
-extern "C" int mi_stem_conv_ok(int C, int K, int R, int S, int stride, int pad, int Q);
-extern "C" int mi_stem_conv_stat_rows(int Nb, int P);
 extern "C" int mi_stem_conv_fwd(const void* x, const void* w, void* y, float* stats, int Nb, int H, int W, int P,
                                 int Q, int pad, hipStream_t st);
 extern "C" int mi_stem_wgrad(const void* x, const void* dy, float* dw, int Nb, int H, int W, int P, int Q, int pad,
                              hipStream_t st);
-static int g_stem = -1;
-static bool use_stem_kernel(int C, int K, int R, int S, int stride, int pad, int Q) {
-  if (g_stem < 0) {
-    const char* e = std::getenv("MI355X_DP_STEM_KERNEL");
-    g_stem = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_stem && mi_stem_conv_ok(C, K, R, S, stride, pad, Q);
-}
 
-// Statistics-slab rows written by mi_conv2d_fwd with stats (full geometry: the halo tiling of
-// 3x3 convs depends on the spatial shape).
+// ---- statistics-slab rows: what the routed kernel writes
+// mi_conv2d_fwd with stats
 MI_API int mi_conv_stat_rows_g(int Nb, int H, int W, int C, int K, int R, int S, int stride, int pad, int P, int Q) {
-  const int M = Nb * P * Q;
-  if (use_stem_kernel(C, K, R, S, stride, pad, Q)) return mi_stem_conv_stat_rows(Nb, P);
-  if (C % 64 == 0 && use_gemm256_conv(M, K, C, R * S * C)) return mi_g256_stat_rows(M, K, R * S * C);
-  if (const int pr = panel_rows_fwd(M, K, C, R, S, pad, H, W, P, Q, stride); pr > 0) return pr;
-  const int rp = C % 64 == 0 ? halo_rp(M, K, R, S, stride, pad, C, H, W, P, Q) : 0;
-  if (rp > 0) return Nb * cdiv(P, rp);
-  return cdiv(M, nt_choice(M, K) == 2 ? 64 : 128);
+  return route_fwd(Nb, H, W, C, K, R, S, stride, pad, P, Q).stat_rows;
 }
-
-// Statistics-slab rows written by a conv forward (M output pixels, N channels, Cs input channels),
-// for shapes outside the halo tiling (1x1 / strided convs, GEMMs).
+// A conv forward known only as a GEMM (M output pixels, N channels, Cs input channels, RS taps), for
+// shapes outside the stem, the halo tiling and the 3x3 panel mode: routed as a 1 x RS filter over M
+// one-pixel images, which has that GEMM and none of those geometries.
 MI_API int mi_conv_stat_rows(int M, int N, int Cs, int RS) {
-  if (use_gemm256_conv(M, N, Cs, RS * Cs)) return mi_g256_stat_rows(M, N, RS * Cs);
-  if (RS == 1 && Cs % 64 == 0)  // a 1x1 (pad 0) conv forward on the panel kernel
-    if (const int pr = mi_panel_stat_rows(M, N, Cs); pr > 0) return pr;
-  const int bm = nt_choice(M, N) == 2 ? 64 : 128;
-  return cdiv(M, bm);
+  return route_fwd(M, 1, 1, Cs, N, 1, RS, 1, 0, 1, 1).stat_rows;
 }
-
-// Rows of the per-channel statistics slab written by a conv/GEMM forward with M rows, N cols.
-MI_API int mi_nt_stat_rows(int M, int N) {
-  const int bm = nt_choice(M, N) == 2 ? 64 : 128;
-  return cdiv(M, bm);
+// mi_conv2d_dgrad_ex4 with stats (epi 4 / 5)
+MI_API int mi_dgrad_stat_rows_g(int Nb, int H, int W, int C, int K, int R, int S, int stride, int pad, int P, int Q) {
+  return route_dgrad(Nb, H, W, C, K, R, S, stride, pad, P, Q, 4, 0).stat_rows;
+}
+// the same for a square filter of RS taps with "same" padding (tests, tools)
+MI_API int mi_dgrad_stat_rows(int Nb, int H, int W, int C, int P, int Q, int stride, int K, int RS) {
+  int R = 1;
+  while ((R + 1) * (R + 1) <= RS) ++R;
+  return mi_dgrad_stat_rows_g(Nb, H, W, C, K, R, R, stride, R / 2, P, Q);
 }
 
 // Conv forward: x NHWC [Nb,H,W,C] bf16, w [K][R][S][C] bf16, y NHWC [Nb,P,Q,K].
-// stats (optional, bf16 output only): fp32 [mi_nt_stat_rows(M,K)][2][K] partial (sum, sumsq).
+// stats (optional, bf16 output only): fp32 [mi_conv_stat_rows_g][2][K] partial (sum, sumsq).
 MI_API int mi_conv2d_fwd(const void* x, const void* w, void* y, const float* bias, float* stats,
                          int Nb, int H, int W, int C, int K, int R, int S,
                          int stride, int pad, int P, int Q, int out_f32, hipStream_t st) {
   if ((C % 64 != 0 && C != 8) || K % 8 != 0) return (int)hipErrorInvalidValue;
-  if (!out_f32 && !bias && use_stem_kernel(C, K, R, S, stride, pad, Q))
-    return mi_stem_conv_fwd(x, w, y, stats, Nb, H, W, P, Q, pad, st);
-  if (!out_f32 && !bias && use_gemm256_conv(Nb * P * Q, K, C, R * S * C))
-    return mi_gemm256_conv(1, x, w, y, stats, 0, nullptr, nullptr, nullptr, 0, Nb, H, W, C, P, Q, R, S, stride, pad,
-                           K, st);
-  if (!out_f32 && !bias && panel_rows_fwd(Nb * P * Q, K, C, R, S, pad, H, W, P, Q, stride) > 0)
-    return mi_panel_conv(x, w, y, stats, Nb, H, W, C, K, R, stride, pad, P, Q, st);
+  const ConvRoute r = route_fwd(Nb, H, W, C, K, R, S, stride, pad, P, Q, out_f32 || bias);
+  switch (r.k) {
+    case ConvKernel::Stem: return mi_stem_conv_fwd(x, w, y, stats, Nb, H, W, P, Q, pad, st);
+    case ConvKernel::G256:
+      return mi_gemm256_conv(1, x, w, y, stats, 0, nullptr, nullptr, nullptr, 0, Nb, H, W, C, P, Q, R, S, stride, pad,
+                             K, 0, nullptr, st);
+    case ConvKernel::Panel: return mi_panel_conv(x, w, y, stats, Nb, H, W, C, K, R, stride, pad, P, Q, st);
+    default: break;  // the NT kernels
+  }
   NTArgs a{};
   a.A = (const bf16_t*)x; a.B = (const bf16_t*)w; a.C = y; a.bias = bias; a.stats = stats;
   a.M = Nb * P * Q; a.N = K; a.K = R * S * C;
@@ -1887,126 +1961,23 @@ MI_API int mi_conv2d_fwd(const void* x, const void* w, void* y, const float* bia
   a.a_bytes = rsrc_bytes((int64_t)Nb * H * W * C);
   a.b_bytes = rsrc_bytes((int64_t)K * a.K);
   a.g = make_geom(H, W, C, P, Q, S, stride, pad, R);
-  return (int)dispatch_nt(a, st);
+  return (int)dispatch_nt(a, st, r);
 }
 
-// Conv backward-data: dy NHWC [Nb,P,Q,K], wt [C][R][S][K] (see mi_conv_wtrans), dx NHWC [Nb,H,W,C].
-MI_API int mi_conv2d_dgrad(const void* dy, const void* wt, void* dx,
-                           int Nb, int H, int W, int C, int K, int R, int S,
-                           int stride, int pad, int P, int Q, hipStream_t st) {
-  if (K % 64 != 0 || C % 8 != 0 || stride > 2) return (int)hipErrorInvalidValue;
-  if (stride == 1 && use_gemm256_conv(Nb * H * W, C, K, R * S * K))
-    return mi_gemm256_conv(2, dy, wt, dx, nullptr, 0, nullptr, nullptr, nullptr, 0, Nb, P, Q, K, H, W, R, S, 1, pad, C,
-                           st);
-  if (R == S && pad == (R == 3 ? 1 : 0) && panel_rows_dgrad(Nb * H * W, C, K, R * S, stride) > 0)
-    return mi_panel_dgrad(dy, wt, dx, Nb, H, W, C, K, R, 0, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, st);
-  NTArgs a{};
-  a.A = (const bf16_t*)dy; a.B = (const bf16_t*)wt; a.C = dx; a.bias = nullptr;
-  a.M = Nb * H * W; a.N = C; a.K = R * S * K;
-  a.lda = 0; a.ldb = a.K; a.ldc = C; a.mode = 2; a.out_f32 = 0; a.accumulate = 0;
-  a.a_bytes = rsrc_bytes((int64_t)Nb * P * Q * K);
-  a.b_bytes = rsrc_bytes((int64_t)C * a.K);
-  // gathered tensor = dy (spatial P,Q, channels K); rows = dx pixels (H, W)
-  a.g = make_geom(P, Q, K, H, W, S, stride, pad, R);
-  if (stride == 2) {
-    // parity-class decomposition: class (ph, pw) rows only visit taps r = ph+pad (mod 2)
-    a.mode = 3;
-    for (int c = 0; c < 4; ++c) {
-      const int ph = c / 2, pw = c % 2;
-      a.g.Pc[c] = (H - ph + 1) / 2;
-      a.g.Qc[c] = (W - pw + 1) / 2;
-      a.g.fPQc[c] = make_fastdiv((uint32_t)std::max(1, a.g.Pc[c] * a.g.Qc[c]));
-      a.g.fQc[c] = make_fastdiv((uint32_t)std::max(1, a.g.Qc[c]));
-      a.cls_map[c] = c;
-    }
-    a.ncls = 4;
-  }
-  return (int)dispatch_nt(a, st);
-}
-
-// Statistics-slab rows written by mi_conv2d_dgrad_ex with stats (all parity classes).
-MI_API int mi_dgrad_stat_rows(int Nb, int H, int W, int C, int P, int Q, int stride, int K, int RS) {
-  const int M = Nb * H * W;
-  if (stride == 1 && use_gemm256_conv(M, C, K, RS * K)) return mi_g256_stat_rows(M, C, RS * K);
-  if (const int pr = panel_rows_dgrad(M, C, K, RS, stride); pr > 0) return pr;
-  const int bm = nt_choice(M, C) == 2 ? 64 : 128;
-  if (stride == 1 && RS == 9) {
-    const int rp = halo_rp(M, C, 3, 3, 1, 1, K, P, Q, H, W);
-    if (rp > 0) return Nb * cdiv(H, rp);
-  }
-  if (stride == 1) return cdiv(M, bm);
-  int mrows = 0;
-  for (int c = 0; c < 4; ++c) mrows = std::max(mrows, Nb * ((H - c / 2 + 1) / 2) * ((W - c % 2 + 1) / 2));
-  return 4 * cdiv(mrows, bm);
-}
-
-// Conv dgrad with a fused epilogue: epi 3 accumulates into aux (dx = dgrad + aux; aux may alias
-// dx -- the residual-gradient sum of a block input), epi 4 emits dz of the BatchNorm that produced
+// Conv backward-data: dy NHWC [Nb,P,Q,K], wt [C][R][S][K] (see mi_conv_wtrans), dx NHWC [Nb,H,W,C],
+// with a fused epilogue: epi 0 none; epi 3 accumulates into aux (dx = dgrad + aux; aux may alias
+// dx -- the residual-gradient sum of a block input); epi 4 emits dz of the BatchNorm that produced
 // this conv's input (aux = BN output y for the relu mask, aux2 = BN input, mean = its batch
-// mean) plus its backward statistics into `stats` ([mi_dgrad_stat_rows][2][C]).
-MI_API int mi_conv2d_dgrad_ex2(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
-                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
-                               const float* mean, int bn_relu, float* stats, int flags, hipStream_t st);
-
-MI_API int mi_conv2d_dgrad_ex(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
-                              int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
-                              const float* mean, int bn_relu, float* stats, hipStream_t st) {
-  return mi_conv2d_dgrad_ex2(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, aux, aux2, mean, bn_relu, stats,
-                             0, st);
-}
-
-// mi_conv2d_dgrad_ex with flags: bit 0 (stride 2, epi 0) leaves the parity classes no tap reaches
-// unwritten instead of zero-filling them (a 1x1 / stride-2 data gradient then writes only the even
-// pixels); bit 1 (epi 3 / 5) reads the accumulated-into gradient only at even (h, w) -- the
-// consumer of such a sparse write.  Together they skip 3/4 of a downsample dgrad's bytes.
-MI_API int mi_conv2d_dgrad_ex3(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
-                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
-                               const float* mean, int bn_relu, float* stats, int flags, const float* mask_scale,
-                               const float* mask_shift, hipStream_t st);
-
-MI_API int mi_conv2d_dgrad_ex2(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
-                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
-                               const float* mean, int bn_relu, float* stats, int flags, hipStream_t st) {
-  return mi_conv2d_dgrad_ex3(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, aux, aux2, mean, bn_relu, stats,
-                             flags, nullptr, nullptr, st);
-}
-
-MI_API int mi_conv2d_dgrad_ex4(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
-                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
-                               const float* mean, int bn_relu, float* stats, int flags, const float* mask_scale,
-                               const float* mask_shift, const void* mbits, hipStream_t st);
-
-MI_API int mi_conv2d_dgrad_ex3(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
-                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
-                               const float* mean, int bn_relu, float* stats, int flags, const float* mask_scale,
-                               const float* mask_shift, hipStream_t st) {
-  return mi_conv2d_dgrad_ex4(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, aux, aux2, mean, bn_relu, stats,
-                             flags, mask_scale, mask_shift, nullptr, st);
-}
-
-extern "C" int mi_gemm256_conv3(int mode, const void* A, const void* B, void* C, float* stats, int epi, void* aux,
-                                const void* aux2, const float* mean, int bn_relu, int Nb, int H, int W, int Cs,
-                                int P, int Q, int R, int S, int stride, int pad, int N, int aux_even,
-                                const void* mbits, hipStream_t st);
-
-// mi_conv2d_dgrad_ex2 with, for epi 4, the ReLU mask of the producing BN taken from its input c (aux2)
+// mean) plus its backward statistics into `stats` ([mi_dgrad_stat_rows_g][2][C]); epi 5 both.
+// flags: bit 0 (stride 2, epi 0) leaves the parity classes no tap reaches unwritten instead of
+// zero-filling them (a 1x1 / stride-2 data gradient then writes only the even pixels); bit 1
+// (epi 3 / 5) reads the accumulated-into gradient only at even (h, w) -- the consumer of such a
+// sparse write.  Together they skip 3/4 of a downsample dgrad's bytes.
+// mask_scale / mask_shift (epi 4): the ReLU mask of the producing BN taken from its input c (aux2)
 // as fma(c, mask_scale, mask_shift) > 0 -- aux (the BN output) unused: normalize-on-load schedules
 // never write it.  Only where mi_conv_nol_ok holds (the 128-tile kernels).
 // mbits (epi 4 / 5 with bn_relu): the ReLU mask as bytes of 8 channel bits ([Nb*H*W][C/8], from
 // mi_bn_apply_bits) instead of reading the BN output aux (which may then be null).
-extern "C" int mi_gemm256_nt_scat2(const void* A, const void* B, void* C, int M, int N, int K, int Q, int W,
-                                   hipStream_t st);
-// MI355X_DP_DS256=0: the stride-2 1x1 shortcut data gradients stay on the 128-tile class kernel
-static int g_ds256 = -1;
-static bool use_ds256() {
-  if (g_ds256 < 0) {
-    const char* e = std::getenv("MI355X_DP_DS256");
-    g_ds256 = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_ds256 != 0;
-}
-MI_API void mi_set_ds256(int on) { g_ds256 = on ? 1 : 0; }
-
 MI_API int mi_conv2d_dgrad_ex4(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
                                int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
                                const float* mean, int bn_relu, float* stats, int flags, const float* mask_scale,
@@ -2019,19 +1990,19 @@ MI_API int mi_conv2d_dgrad_ex4(const void* dy, const void* wt, void* dx, int Nb,
       ((flags & 1) && (stride != 2 || epi != 0)) || ((flags & 2) && epi != 3 && epi != 5))
     return (int)hipErrorInvalidValue;
   const int aux_even = (flags >> 1) & 1;
-  if (mask_c && stride == 1 && use_gemm256_conv(Nb * H * W, C, K, R * S * K)) return (int)hipErrorNotSupported;
-  if (stride == 1 && use_gemm256_conv(Nb * H * W, C, K, R * S * K))
-    return mi_gemm256_conv3(2, dy, wt, dx, epi >= 4 ? stats : nullptr, epi, const_cast<void*>(aux), aux2, mean,
-                            bn_relu, Nb, P, Q, K, H, W, R, S, 1, pad, C, aux_even, mbits, st);
-  // the stride-2 1x1 data gradient of a projection shortcut (only the even pixels, flags bit 0) as a
-  // plain GEMM over dy's pixels on the 256-wide kernel, rows scattered to the even pixels of dx
-  if (stride == 2 && R == 1 && S == 1 && pad == 0 && epi == 0 && (flags & 1) && !mask_c && !mbits && H == 2 * P &&
-      W == 2 * Q && use_ds256() && use_gemm256_conv(Nb * P * Q, C, K, K))
-    return mi_gemm256_nt_scat2(dy, wt, dx, Nb * P * Q, C, K, Q, W, st);
-  if (R == S && pad == (R == 3 ? 1 : 0) && panel_rows_dgrad(Nb * H * W, C, K, R * S, stride) > 0) {
-    if (mask_c) return (int)hipErrorNotSupported;  // mi_conv_nol_ok keeps these shapes materialised
-    return mi_panel_dgrad(dy, wt, dx, Nb, H, W, C, K, R, epi, aux, aux2, mean, bn_relu, stats, aux_even, mbits,
-                          nullptr, st);
+  const ConvRoute r = route_dgrad(Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, flags);
+  switch (r.k) {
+    case ConvKernel::G256:
+      if (mask_c) return (int)hipErrorNotSupported;  // mi_conv_nol_ok keeps these shapes materialised
+      return mi_gemm256_conv(2, dy, wt, dx, epi >= 4 ? stats : nullptr, epi, const_cast<void*>(aux), aux2, mean,
+                             bn_relu, Nb, P, Q, K, H, W, R, S, 1, pad, C, aux_even, mbits, st);
+    case ConvKernel::G256Scatter:  // epi 0: no mask of either kind
+      return mi_gemm256_nt_scat2(dy, wt, dx, Nb * P * Q, C, K, Q, W, st);
+    case ConvKernel::Panel:
+      if (mask_c) return (int)hipErrorNotSupported;  // likewise
+      return mi_panel_dgrad(dy, wt, dx, Nb, H, W, C, K, R, epi, aux, aux2, mean, bn_relu, stats, aux_even, mbits,
+                            nullptr, st);
+    default: break;  // the NT kernels
   }
   NTArgs a{};
   a.A = (const bf16_t*)dy; a.B = (const bf16_t*)wt; a.C = dx; a.bias = nullptr;
@@ -2044,8 +2015,10 @@ MI_API int mi_conv2d_dgrad_ex4(const void* dy, const void* wt, void* dx, int Nb,
   a.mbits = (const uint8_t*)mbits;
   a.a_bytes = rsrc_bytes((int64_t)Nb * P * Q * K);
   a.b_bytes = rsrc_bytes((int64_t)C * a.K);
+  // gathered tensor = dy (spatial P,Q, channels K); rows = dx pixels (H, W)
   a.g = make_geom(P, Q, K, H, W, S, stride, pad, R);
-  if (stride == 2) {
+  if (r.k == ConvKernel::NtClasses) {
+    // parity-class decomposition: class (ph, pw) rows only visit taps r = ph+pad (mod 2)
     a.mode = 3;
     a.ncls = 0;
     for (int c = 0; c < 4; ++c) {
@@ -2060,7 +2033,33 @@ MI_API int mi_conv2d_dgrad_ex4(const void* dy, const void* wt, void* dx, int Nb,
     }
     if (a.ncls == 0) return (int)hipSuccess;
   }
-  return (int)dispatch_nt(a, st);
+  return (int)dispatch_nt(a, st, r);
+}
+
+// the earlier, shorter signatures of mi_conv2d_dgrad_ex4 (tests, tools)
+MI_API int mi_conv2d_dgrad_ex3(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
+                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
+                               const float* mean, int bn_relu, float* stats, int flags, const float* mask_scale,
+                               const float* mask_shift, hipStream_t st) {
+  return mi_conv2d_dgrad_ex4(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, aux, aux2, mean, bn_relu, stats,
+                             flags, mask_scale, mask_shift, nullptr, st);
+}
+MI_API int mi_conv2d_dgrad_ex2(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
+                               int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
+                               const float* mean, int bn_relu, float* stats, int flags, hipStream_t st) {
+  return mi_conv2d_dgrad_ex4(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, aux, aux2, mean, bn_relu, stats,
+                             flags, nullptr, nullptr, nullptr, st);
+}
+MI_API int mi_conv2d_dgrad_ex(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R,
+                              int S, int stride, int pad, int P, int Q, int epi, const void* aux, const void* aux2,
+                              const float* mean, int bn_relu, float* stats, hipStream_t st) {
+  return mi_conv2d_dgrad_ex4(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, epi, aux, aux2, mean, bn_relu, stats,
+                             0, nullptr, nullptr, nullptr, st);
+}
+MI_API int mi_conv2d_dgrad(const void* dy, const void* wt, void* dx, int Nb, int H, int W, int C, int K, int R, int S,
+                           int stride, int pad, int P, int Q, hipStream_t st) {
+  return mi_conv2d_dgrad_ex4(dy, wt, dx, Nb, H, W, C, K, R, S, stride, pad, P, Q, 0, nullptr, nullptr, nullptr, 0,
+                             nullptr, 0, nullptr, nullptr, nullptr, st);
 }
 
 // MI355X_DP_WGRAD256=T (T >= 1): a 1x1 stride-1 weight gradient with >= T output tiles of 256 x 256
@@ -2068,18 +2067,10 @@ MI_API int mi_conv2d_dgrad_ex4(const void* dy, const void* wt, void* dx, int Nb,
 // 128-tile implicit-GEMM kernel; 0 (default): never
 extern "C" int mi_gemm256_tn(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                              hipStream_t st);
-static int g_wgrad256 = -1;
 static bool use_wgrad256(int K, int C, int R, int S, int stride, int pad, int H, int W, int P, int Q) {
-  if (g_wgrad256 < 0) {
-    const char* e = std::getenv("MI355X_DP_WGRAD256");
-    g_wgrad256 = e ? std::max(0, std::atoi(e)) : 0;
-  }
-  return g_wgrad256 > 0 && R == 1 && S == 1 && stride == 1 && pad == 0 && P == H && Q == W && K % 8 == 0 &&
-         C % 8 == 0 && cdiv(K, 256) * cdiv(C, 256) >= g_wgrad256;
-}
-MI_API void mi_set_wgrad256(int min_tiles) {
-  use_wgrad256(0, 0, 0, 0, 0, 0, 0, 0, 0, 0);  // env init
-  g_wgrad256 = std::max(0, min_tiles);
+  const int t = sw().wgrad256;
+  return t > 0 && R == 1 && S == 1 && stride == 1 && pad == 0 && P == H && Q == W && K % 8 == 0 && C % 8 == 0 &&
+         cdiv(K, 256) * cdiv(C, 256) >= t;
 }
 
 // Conv backward-weight: dw[K][R][S][C] (fp32) += sum over pixels dy^T * im2col(x).
@@ -2101,26 +2092,15 @@ MI_API int mi_conv2d_wgrad(const void* x, const void* dy, float* dw,
   return (int)dispatch_tn(a, st);
 }
 
-// ---- folded BatchNorm backward, data-gradient routing: the panel kernel when the doubled depth fits
-// its LDS (conv_panel.hip), else the 256-wide kernel where the unfolded data gradient runs there
-// (gemm256.hip mi_gemm256_dgrad_fbb); 0: not eligible (the caller materialises dX)
-extern "C" int mi_panel_fbb_rows(int M, int C, int K);
-extern "C" int mi_gemm256_dgrad_fbb(const void* dz, const void* c, const float* coef, const void* wt, void* wq,
-                                    float* bias, void* dx, float* stats, int epi, void* aux, const void* aux2,
-                                    const float* mean, int bn_relu, int Nb, int H, int W, int C, int K, int aux_even,
-                                    const void* mbits, hipStream_t st);
+// ---- folded BatchNorm backward, data-gradient routing (route_dgrad_fold): 1 = the panel kernel
+// (mi_panel_dgrad_fbb), 2 = the 256-wide kernel (mi_gemm256_dgrad_fbb), 0 = not eligible
 MI_API int mi_conv_fbb_route(int M, int C, int K) {
-  if (K % 64 != 0 || C % 64 != 0) return 0;
-  if (mi_panel_fbb_rows(M, C, K) > 0) return 1;
-  if (use_gemm256_conv(M, C, K, K)) return 2;
-  return 0;
+  const ConvKernel k = route_dgrad_fold(M, C, K).k;
+  return k == ConvKernel::Panel ? 1 : (k == ConvKernel::G256 ? 2 : 0);
 }
 
 // statistics slab rows of the folded data gradient (route 1 or 2), 0 if not eligible
-MI_API int mi_conv_fbb_rows(int M, int C, int K) {
-  const int r = mi_conv_fbb_route(M, C, K);
-  return r == 1 ? mi_panel_fbb_rows(M, C, K) : (r == 2 ? mi_g256_stat_rows(M, C, 2 * K) : 0);
-}
+MI_API int mi_conv_fbb_rows(int M, int C, int K) { return route_dgrad_fold(M, C, K).stat_rows; }
 
 // ---- folded BatchNorm backward, weight-gradient side (conv_panel.hip mi_panel_dgrad_fbb): the weight
 // gradient of a 1x1 / stride-1 conv against its output's BN input gradient dX = k0 dz + k1 c + k2 (per
@@ -2214,15 +2194,13 @@ MI_API int mi_conv2d_wgrad_fbb(const void* x, const void* dz, const void* w, con
 // kernel; shapes routed to the stem or 256x256 kernels keep the materialised BN output.
 MI_API int mi_conv_nol_ok(int Nb, int H, int W, int C, int K, int R, int S, int stride, int pad, int P, int Q) {
   if (C % 64 != 0 || C > NOL_MAX_C || K % 64 != 0 || stride > 2 || !glds_on()) return 0;
-  if (use_stem_kernel(C, K, R, S, stride, pad, Q)) return 0;
-  if (use_gemm256_conv(Nb * P * Q, K, C, R * S * C)) return 0;                    // forward
-  if (panel_rows_fwd(Nb * P * Q, K, C, R, S, pad, H, W, P, Q, stride) > 0) return 0;  // forward (panel)
-  if (panel_rows_dgrad(Nb * H * W, C, K, R * S, stride) > 0) return 0;               // data gradient (panel)
-  if (stride == 1 && use_gemm256_conv(Nb * H * W, C, K, R * S * K)) return 0;    // data gradient
+  const ConvRoute f = route_fwd(Nb, H, W, C, K, R, S, stride, pad, P, Q);
+  const ConvRoute d = route_dgrad(Nb, H, W, C, K, R, S, stride, pad, P, Q, 4, 0);
+  if (f.k != ConvKernel::Nt && f.k != ConvKernel::NtHalo) return 0;
+  if (d.k != ConvKernel::Nt && d.k != ConvKernel::NtHalo && d.k != ConvKernel::NtClasses) return 0;
   // small grids keep the materialised path: there the 128-tile kernels split K (nt_split_blocks),
   // which the normalize-on-load variants do not -- and the bytes saved are negligible
-  const int tf = cdiv(Nb * P * Q, nt_choice(Nb * P * Q, K) == 2 ? 64 : 128) * cdiv(K, nt_choice(Nb * P * Q, K) == 0 ? 128 : 64);
-  const int td = cdiv(Nb * H * W, nt_choice(Nb * H * W, C) == 2 ? 64 : 128) * cdiv(C, nt_choice(Nb * H * W, C) == 0 ? 128 : 64);
+  const int tf = cdiv(Nb * P * Q, f.bm) * cdiv(K, f.bn), td = cdiv(Nb * H * W, d.bm) * cdiv(C, d.bn);
   if (tf < nt_split_blocks() || td < nt_split_blocks()) return 0;
   return 1;
 }
@@ -2240,7 +2218,7 @@ MI_API int mi_conv2d_fwd_nol(const void* x, const void* w, void* y, float* stats
   a.a_bytes = rsrc_bytes((int64_t)Nb * H * W * C);
   a.b_bytes = rsrc_bytes((int64_t)K * a.K);
   a.g = make_geom(H, W, C, P, Q, S, stride, pad, R);
-  return (int)dispatch_nt(a, st);
+  return (int)dispatch_nt(a, st, route_fwd(Nb, H, W, C, K, R, S, stride, pad, P, Q));  // Nt / NtHalo: nol_ok
 }
 
 MI_API int mi_conv2d_wgrad_nol(const void* x, const void* dy, float* dw, const float* nol_scale,
@@ -2278,29 +2256,16 @@ MI_API int mi_conv_wtrans_multi(const void* w, void* wt, const void* desc, int n
 // chip with at least one wave of 256x256 tiles; MI355X_DP_GEMM256=0 disables it (A/B runs).
 extern "C" int mi_gemm256_nt(const void* A, const void* B, void* C, const float* bias, void* aux, int epi, int M,
                              int N, int K, int lda, int ldb, int ldc, int out_f32, int accumulate, hipStream_t st);
-static int g_gemm256 = -1;
 static bool use_gemm256(int M, int N, int K) {
-  if (g_gemm256 < 0) {
-    const char* e = getenv("MI355X_DP_GEMM256");
-    g_gemm256 = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_gemm256 && K >= 128 && (int64_t)cdiv(M, 256) * cdiv(N, 256) >= 256;
+  return sw().gemm256 && K >= 128 && (int64_t)cdiv(M, 256) * cdiv(N, 256) >= 256;
 }
-
-MI_API void mi_set_gemm256(int on) { g_gemm256 = on ? 1 : 0; }
 
 // TN: the 256x256 kernel wins only without heavy split-K (>= 128 output tiles); weight-gradient
 // shapes with few output tiles (ViT: 9-36) stay on the 128x128 split-K kernel (L2 locality).
 extern "C" int mi_gemm256_tn(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                              hipStream_t st);
-static int g_tn256_min_tiles = -1;
 static bool use_gemm256_tn(int M, int N, int K) {
-  use_gemm256(0, 0, 0);  // env init
-  if (g_tn256_min_tiles < 0) {
-    const char* e = std::getenv("MI355X_DP_TN256_MIN_TILES");
-    g_tn256_min_tiles = e ? std::max(1, std::atoi(e)) : 128;
-  }
-  return g_gemm256 && K >= 1024 && (int64_t)cdiv(M, 256) * cdiv(N, 256) >= g_tn256_min_tiles;
+  return sw().gemm256 && K >= 1024 && (int64_t)cdiv(M, 256) * cdiv(N, 256) >= sw().tn256_min_tiles;
 }
 
 // Plain GEMM, "NT": C[M][N] = A[M][K] * B[N][K]^T (+bias[N]); A, B bf16; C bf16 or fp32.

@@ -40,7 +40,7 @@ from .functional import BF16, CL, _finish_grad, _grad_buffer, _nhwc, _side, run_
 
 F32 = torch.float32
 EPI_ACCUM, EPI_BN_BWD, EPI_ACCUM_BN_BWD = 3, 4, 5
-# mi_conv2d_dgrad_ex2 flags: write only the parity classes some tap reaches (stride 2) / read the
+# mi_conv2d_dgrad_ex4 flags: write only the parity classes some tap reaches (stride 2) / read the
 # accumulated-into gradient only at even (h, w)
 DGRAD_SPARSE, DGRAD_ACC_EVEN = 1, 2
 
@@ -228,20 +228,25 @@ def _wgrad(x, dy, spec, nol=None):
     return _finish_grad(spec.w, g)
 
 
-def _dgrad(dy, spec, x_shape, out, epi=0, aux=None, aux2=None, mean=None, relu=0, stats=None, flags=0, mbits=None):
+def _dgrad(dy, spec, x_shape, out, epi=0, aux=None, aux2=None, mean=None, relu=0, stats=None, flags=0, mbits=None,
+           mask=None):
+    """mbits: ReLU mask bytes instead of the bf16 BN output (epi 4 / 5); mask: (scale, shift) of the
+    producing BN, the mask taken from its input aux2 (epi 4, normalize-on-load)."""
     N, C, H, W = x_shape
     K, _, R, S = spec.w.shape
     P, Q = dy.shape[2], dy.shape[3]
-    st = stream_of(dy)
-    wt = weight_bf16_t(spec.w)
-    if mbits is not None:  # ReLU mask bytes instead of the bf16 BN output (epi 4 / 5)
-        _lib.call("mi_conv2d_dgrad_ex4", ptr(dy), ptr(wt), ptr(out), N, H, W, C, K, R, S, spec.stride, spec.pad, P,
-                  Q, int(epi), ptr(aux), ptr(aux2), ptr(mean), int(relu), ptr(stats), int(flags), ptr(None),
-                  ptr(None), ptr(mbits), st)
-        return out
-    _lib.call("mi_conv2d_dgrad_ex2", ptr(dy), ptr(wt), ptr(out), N, H, W, C, K, R, S, spec.stride, spec.pad, P, Q,
-              int(epi), ptr(aux), ptr(aux2), ptr(mean), int(relu), ptr(stats), int(flags), st)
+    ms, mh = mask if mask is not None else (None, None)
+    _lib.call("mi_conv2d_dgrad_ex4", ptr(dy), ptr(weight_bf16_t(spec.w)), ptr(out), N, H, W, C, K, R, S, spec.stride,
+              spec.pad, P, Q, int(epi), ptr(aux), ptr(aux2), ptr(mean), int(relu), ptr(stats), int(flags), ptr(ms),
+              ptr(mh), ptr(mbits), stream_of(dy))
     return out
+
+
+def _dgrad_rows(spec, x_shape, dy):
+    """statistics-slab rows _dgrad's kernel writes (epi 4 / 5)"""
+    N, C, H, W = x_shape
+    K, _, R, S = spec.w.shape
+    return _lib.load().mi_dgrad_stat_rows_g(N, H, W, C, K, R, S, spec.stride, spec.pad, dy.shape[2], dy.shape[3])
 
 
 def _dgrad_bn(dy, spec, y_prev, c_prev, mean_prev, mask=None, bits=None):
@@ -257,18 +262,13 @@ def _dgrad_bn(dy, spec, y_prev, c_prev, mean_prev, mask=None, bits=None):
         dz = torch.empty_like(c_prev, memory_format=CL)
         _dgrad_fold(dy, spec, c_prev.shape, dz, EPI_BN_BWD, y_prev, c_prev, mean_prev, 1, slab, mbits=bits)
         return dz, slab, rows
-    rows = lib.mi_dgrad_stat_rows(N, H, W, C, dy.shape[2], dy.shape[3], spec.stride, spec.w.shape[0],
-                                 spec.w.shape[2] * spec.w.shape[3])
+    rows = _dgrad_rows(spec, c_prev.shape, dy)
     slab = torch.empty((rows + lib.mi_bn_slab_extra_rows(), 2, C), dtype=F32, device=dy.device)
     dz = torch.empty_like(c_prev, memory_format=CL)
     if mask is not None:
-        K, _, R, S = spec.w.shape
-        P, Q = dy.shape[2], dy.shape[3]
-        _lib.call("mi_conv2d_dgrad_ex3", ptr(dy), ptr(weight_bf16_t(spec.w)), ptr(dz), N, H, W, C, K, R, S,
-                  spec.stride, spec.pad, P, Q, EPI_BN_BWD, ptr(None), ptr(c_prev), ptr(mean_prev), 1, ptr(slab), 0,
-                  ptr(mask[0]), ptr(mask[1]), stream_of(dy))
-        return dz, slab, rows
-    _dgrad(dy, spec, c_prev.shape, dz, EPI_BN_BWD, y_prev, c_prev, mean_prev, 1, slab, mbits=bits)
+        _dgrad(dy, spec, c_prev.shape, dz, EPI_BN_BWD, None, c_prev, mean_prev, 1, slab, mask=mask)
+    else:
+        _dgrad(dy, spec, c_prev.shape, dz, EPI_BN_BWD, y_prev, c_prev, mean_prev, 1, slab, mbits=bits)
     return dz, slab, rows
 
 
@@ -621,8 +621,7 @@ class _ResBlock(torch.autograd.Function):
             c_prev, m_prev, bits_prev = ctx.prev_bnsrc
             N, C, H, W = x.shape
             lib = _lib.load()
-            rows = lib.mi_dgrad_stat_rows(N, H, W, C, dc.shape[2], dc.shape[3], convs[0].stride,
-                                          convs[0].w.shape[0], convs[0].w.shape[2] * convs[0].w.shape[3])
+            rows = _dgrad_rows(convs[0], x.shape, dc)
             if isinstance(dc, _Fold):
                 rows = lib.mi_conv_fbb_rows(N * H * W, C, convs[0].w.shape[0])
             elif acc_src is not None:
