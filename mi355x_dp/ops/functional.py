@@ -740,6 +740,212 @@ def adamw_flat_(params, grads, exp_avg, exp_avg_sq, params_bf16, state, beta1, b
               ptr(state), ptr(decay_map), int(unit_base), float(beta1), float(beta2), float(eps), stream_of(params))
 
 
+# layer-wise optimizers (second half of csrc/kernels/optim.hip).  Every range is whole 64-element
+# units; a unit belongs to one parameter or to none (``pidx < 0``).  Device state blocks, float64:
+#   LARS  [0] step t  [1] lr
+#   LAMB  [0] step t  [1] lr  [2] total_norm  [3] clip coefficient  [4] bc1  [5] bc2
+#         [6] grad_scale * coef  [7] unused
+LARS_STATE_LEN = 2
+LAMB_STATE_LEN = 8
+SEG_UNIT = 64
+
+
+def _unit_lookup(pidx, excl, q, unit_base, n):
+    """host: per-element (excluded, q) of ``n`` elements starting at unit ``unit_base``"""
+    idx = pidx[unit_base:unit_base + n // SEG_UNIT].long()
+    safe = idx.clamp(min=0)
+    ex = (idx < 0) | (excl[safe] != 0)
+    qu = None if q is None else torch.where(ex, torch.ones((), dtype=torch.float32), q[safe])
+    rep = lambda t: None if t is None else t.repeat_interleave(SEG_UNIT)  # noqa: E731
+    return rep(ex), rep(qu)
+
+
+def seg_sqnorm_units_(x, part, y=None, part_y=None):
+    """Pass 1 of the segmented norms: ``part[u]`` (float64) = sum of squares of the fp32 elements
+    ``x[64 u : 64 u + 64]``; with ``y`` also ``part_y[u]`` from ``y`` in the same launch.  The bits of
+    a unit's partial depend on its 64 values alone."""
+    n = x.numel()
+    assert n % SEG_UNIT == 0 and part.dtype == torch.float64 and part.numel() >= n // SEG_UNIT
+    if y is not None:
+        assert y.numel() == n and part_y.dtype == torch.float64 and part_y.numel() >= n // SEG_UNIT
+    if not x.is_cuda:
+        with torch.no_grad():
+            for src, dst in ((x, part), (y, part_y)):
+                if src is not None:
+                    dst[:n // SEG_UNIT] = src.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
+        return
+    for t in (x, y):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    assert part.is_contiguous() and (part_y is None or part_y.is_contiguous())
+    _lib.call("mi_seg_sqnorm_units", ptr(x), ptr(y), n, ptr(part), ptr(part_y), stream_of(x))
+
+
+def seg_sqnorm_reduce_(parts, table, out):
+    """Pass 2: ``out[s * P + p]`` = sum of ``parts[s, table[p, 0]:table[p, 1]]`` in a fixed order
+    that depends on the range alone.  ``parts``: float64 ``[nsets, U]`` (or ``[U]``) unit partials,
+    ``table``: int64 ``[P, 2]`` unit ranges (may be empty), ``out``: float64, ``nsets * P``."""
+    parts2 = parts.reshape(1, -1) if parts.dim() == 1 else parts
+    nsets, stride = parts2.shape
+    P = table.shape[0]
+    assert table.dtype == torch.int64 and table.shape == (P, 2) and table.is_contiguous()
+    assert out.dtype == torch.float64 and out.numel() >= nsets * P and parts2.dtype == torch.float64
+    if not out.is_cuda:
+        with torch.no_grad():
+            flat = out.reshape(-1)
+            for s in range(nsets):
+                for p, (lo, hi) in enumerate(table.tolist()):
+                    flat[s * P + p] = parts2[s, lo:hi].sum()
+        return out
+    assert parts2.is_contiguous() and out.is_contiguous()
+    _lib.call("mi_seg_sqnorm_reduce", ptr(parts2), int(stride), int(nsets), ptr(table), int(P), ptr(out),
+              stream_of(out))
+    return out
+
+
+def lars_trust_(sums, excl, q, state, trust_coefficient, weight_decay, eps, grad_scale=1.0):
+    """``q[p]`` (float32) from ``sums`` = [sum w^2 per parameter | sum g^2 per parameter] (float64,
+    g unscaled): ``tc * |w| / (grad_scale * |g| + wd * |w| + eps)`` where both norms are > 0 and
+    the parameter is not excluded, else 1.  Advances ``state[0]`` (the step counter)."""
+    P = excl.numel()
+    assert sums.numel() >= 2 * P and q.numel() >= P
+    if not sums.is_cuda:
+        with torch.no_grad():
+            wn = sums[:P].sqrt()
+            gn = grad_scale * sums[P:2 * P].sqrt()
+            r = trust_coefficient * wn / (gn + weight_decay * wn + eps)
+            ok = (excl == 0) & (wn > 0) & (gn > 0)
+            q[:P] = torch.where(ok, r, torch.ones_like(r)).float()
+            state[0] += 1.0
+        return
+    assert sums.dtype == torch.float64 and excl.dtype == torch.uint8 and q.dtype == torch.float32
+    assert state.dtype == torch.float64 and state.numel() >= LARS_STATE_LEN
+    _lib.call("mi_lars_trust", ptr(sums), ptr(excl), ptr(q), ptr(state), int(P), float(trust_coefficient),
+              float(weight_decay), float(eps), float(grad_scale), stream_of(sums))
+
+
+def lamb_trust_(sums, excl, q):
+    """``q[p]`` = ``|w| / |u|`` from ``sums`` = [sum w^2 | sum u^2] where both are > 0 and the
+    parameter is not excluded, else 1."""
+    P = excl.numel()
+    assert sums.numel() >= 2 * P and q.numel() >= P
+    if not sums.is_cuda:
+        with torch.no_grad():
+            wn, un = sums[:P].sqrt(), sums[P:2 * P].sqrt()
+            ok = (excl == 0) & (wn > 0) & (un > 0)
+            q[:P] = torch.where(ok, wn / un, torch.ones_like(wn)).float()
+        return
+    assert sums.dtype == torch.float64 and excl.dtype == torch.uint8 and q.dtype == torch.float32
+    _lib.call("mi_lamb_trust", ptr(sums), ptr(excl), ptr(q), int(P), stream_of(sums))
+
+
+def _check_units(n, pidx, unit_base, *tensors):
+    assert n % SEG_UNIT == 0, "layer-wise kernels take whole 64-element units"
+    assert pidx.dtype == torch.int32 and pidx.numel() >= unit_base + n // SEG_UNIT and unit_base >= 0
+    for t in tensors:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+
+
+def lars_flat_(params, grads, momentum_buf, params_bf16, state, pidx, excl, q, unit_base, momentum, weight_decay,
+               grad_scale=1.0):
+    """One fused LARS update over whole units of the flat buffers (+ bf16 compute-copy refresh):
+    ``g' = grad_scale * g``; ``d = q * (g' + wd * w)``, for excluded units ``d = g'``;
+    ``buf = momentum * buf + d``; ``w -= lr * buf`` with ``lr = state[1]``.  ``pidx``: int32 parameter
+    index per unit of the whole flat buffer (< 0: no parameter), ``excl`` / ``q`` per parameter."""
+    n = params.numel()
+    _check_units(n, pidx, unit_base, params, grads, momentum_buf)
+    if not params.is_cuda:
+        with torch.no_grad():
+            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
+            ex, qe = _unit_lookup(pidx, excl, q, unit_base, n)
+            g = grads * f32(grad_scale)
+            d = torch.where(ex, g, qe * (g + f32(weight_decay) * params))
+            momentum_buf.mul_(f32(momentum)).add_(d)
+            params.sub_(f32(float(state[1])) * momentum_buf)
+            if params_bf16 is not None:
+                params_bf16.copy_(params)
+        return
+    _lib.call("mi_lars_flat", ptr(params), ptr(grads), ptr(momentum_buf), ptr(params_bf16), n, ptr(state),
+              ptr(pidx), ptr(excl), ptr(q), int(unit_base), float(momentum), float(weight_decay), float(grad_scale),
+              stream_of(params))
+
+
+def lamb_prep_(state, sumsq, beta1, beta2, max_norm=None, grad_scale=1.0):
+    """Advance the LAMB step counter and derive the bias corrections and, when ``max_norm`` is
+    given, the clip coefficient from the squared gradient norm ``sumsq`` (as ``adamw_prep_``)."""
+    clip = max_norm is not None
+    if not state.is_cuda:
+        import math
+        with torch.no_grad():
+            t = float(state[0]) + 1.0
+            coef = 1.0
+            if clip:
+                total = grad_scale * math.sqrt(float(sumsq.reshape(-1)[0]))
+                c = float(max_norm) / (total + 1e-6)
+                coef = 1.0 if c > 1.0 else c
+                state[2] = total
+            state[0] = t
+            state[3] = coef
+            state[4] = 1.0 - beta1 ** t
+            state[5] = 1.0 - beta2 ** t
+            state[6] = grad_scale * coef
+        return
+    assert state.dtype == torch.float64 and state.numel() >= LAMB_STATE_LEN
+    _lib.call("mi_lamb_prep", ptr(state), ptr(sumsq) if clip else ptr(None), float(beta1), float(beta2),
+              float(max_norm) if clip else 0.0, float(grad_scale), int(clip), stream_of(state))
+
+
+def _lamb_u_host(params, exp_avg, exp_avg_sq, ex, state, eps, weight_decay):
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
+    r = (exp_avg / f32(float(state[4]))) / ((exp_avg_sq / f32(float(state[5]))).sqrt() + f32(eps))
+    return torch.where(ex, r, r + f32(weight_decay) * params)
+
+
+def lamb_moments_(params, grads, exp_avg, exp_avg_sq, state, pidx, excl, unit_base, part_w, part_u, beta1, beta2,
+                  eps, weight_decay):
+    """LAMB, first launch of a segment: ``m``, ``v`` updated from ``g' = state[6] * g``;
+    ``u = (m / bc1) / (sqrt(v / bc2) + eps) + wd * w`` (excluded units: no ``wd * w``) is formed in
+    registers and its per-unit sums of squares go to ``part_u``, those of ``w`` to ``part_w`` (float64,
+    one per unit of this range, the scheme of ``seg_sqnorm_units_``).  ``params`` is not written."""
+    n = params.numel()
+    _check_units(n, pidx, unit_base, params, grads, exp_avg, exp_avg_sq)
+    for t in (part_w, part_u):
+        assert t.dtype == torch.float64 and t.numel() >= n // SEG_UNIT and t.is_contiguous()
+    if not params.is_cuda:
+        with torch.no_grad():
+            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
+            ex, _ = _unit_lookup(pidx, excl, None, unit_base, n)
+            g = grads * f32(float(state[6]))
+            exp_avg.mul_(f32(beta1)).add_(g, alpha=f32(1.0 - beta1))
+            exp_avg_sq.mul_(f32(beta2)).add_(g * g, alpha=f32(1.0 - beta2))
+            u = _lamb_u_host(params, exp_avg, exp_avg_sq, ex, state, eps, weight_decay)
+            part_w[:n // SEG_UNIT] = params.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
+            part_u[:n // SEG_UNIT] = u.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
+        return
+    _lib.call("mi_lamb_moments", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), n, ptr(state), ptr(pidx),
+              ptr(excl), int(unit_base), ptr(part_w), ptr(part_u), float(beta1), float(beta2), float(eps),
+              float(weight_decay), stream_of(params))
+
+
+def lamb_apply_(params, exp_avg, exp_avg_sq, params_bf16, state, pidx, excl, q, unit_base, beta1, beta2, eps,
+                weight_decay):
+    """LAMB, second launch of a segment: ``w -= lr * q * u`` with ``u`` recomputed from the stored
+    moments and the still unchanged ``w`` (+ bf16 compute-copy refresh)."""
+    n = params.numel()
+    _check_units(n, pidx, unit_base, params, exp_avg, exp_avg_sq)
+    if not params.is_cuda:
+        with torch.no_grad():
+            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
+            ex, qe = _unit_lookup(pidx, excl, q, unit_base, n)
+            u = _lamb_u_host(params, exp_avg, exp_avg_sq, ex, state, eps, weight_decay)
+            params.sub_((f32(float(state[1])) * qe) * u)
+            if params_bf16 is not None:
+                params_bf16.copy_(params)
+        return
+    _lib.call("mi_lamb_apply", ptr(params), ptr(exp_avg), ptr(exp_avg_sq), ptr(params_bf16), n, ptr(state), ptr(pidx),
+              ptr(excl), ptr(q), int(unit_base), float(beta1), float(beta2), float(eps), float(weight_decay),
+              stream_of(params))
+
+
 def cast_bf16_(src, dst):
     if not src.is_cuda:
         dst.copy_(src)

@@ -10,6 +10,16 @@ events around ``--steps`` (>= 100) back-to-back steps.  Bytes are computed from 
 norm pass when clipping.
 
     python tools/bench_optim.py [--steps 200] [--rounds 5] [--out profiles/adamw_flat.json]
+
+``--suite layerwise`` times ``FlatLARS`` and ``FlatLAMB`` instead, interleaved in the same process
+with the optimizer each extends (``FlatSGD`` with momentum, ``FlatAdamW``) on the same engine, and
+then every layer-wise kernel on its own over the whole flat buffer (device events around
+``--steps`` back-to-back launches).  Bytes per element: SGD 22 (p, buf read and written, g read,
+bf16 written), LARS 30 (+ the norm pass reading p and g), AdamW 30, LAMB 42 (moments: p, g, m, v
+read, m, v written = 24; apply: p, m, v read, p and bf16 written = 18); the fp64 unit partials add
+8 B per 64 elements and array.
+
+    python tools/bench_optim.py --suite layerwise [--out profiles/layerwise_optim.json]
 """
 import argparse
 import json
@@ -87,6 +97,81 @@ def bench_model(name, steps, rounds, warmup):
             "rounds": rounds, "results": rows, "errors": errors}
 
 
+def _rows(ms, nbytes):
+    rows = {}
+    for k, v in ms.items():
+        med = statistics.median(v)
+        rows[k] = {"ms_median": round(med, 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4),
+                   "bytes": nbytes[k], "TBps_at_median": round(nbytes[k] / (med * 1e-3) / 1e12, 3)}
+    return rows
+
+
+def bench_layerwise(name, steps, rounds, warmup):
+    """FlatSGD / FlatLARS / FlatAdamW / FlatLAMB steps interleaved on one engine, then the
+    layer-wise kernels one by one over the whole flat buffer"""
+    from mi355x_dp import ops
+    from mi355x_dp.models import get_model
+    from mi355x_dp.parallel import DataParallel, FlatAdamW, FlatLAMB, FlatLARS, FlatSGD
+    torch.manual_seed(0)
+    eng = DataParallel(get_model(name).cuda())
+    f = eng.flat
+    f.grad.normal_(std=1e-2)
+    sgd = FlatSGD(eng, lr=1e-3, momentum=0.9, weight_decay=1e-4)
+    lars = FlatLARS(eng, lr=1e-3, momentum=0.9, weight_decay=1e-4)
+    adamw = FlatAdamW(eng, lr=1e-4, weight_decay=0.05)
+    lamb = FlatLAMB(eng, lr=1e-4, weight_decay=0.01)
+    lamb_clip = FlatLAMB(eng, lr=1e-4, weight_decay=0.01, max_grad_norm=1.0)
+    sides = {"flat_sgd": sgd.step, "flat_lars": lars.step, "flat_adamw": adamw.step, "flat_lamb": lamb.step,
+             "flat_lamb_clip": lamb_clip.step}
+    n = f.numel
+    units = n // 64
+    per_elem = {"flat_sgd": 22, "flat_lars": 30, "flat_adamw": 30, "flat_lamb": 42, "flat_lamb_clip": 46}
+    nbytes = {k: n * b + (16 * units if "lars" in k or "lamb" in k else 0) for k, b in per_elem.items()}
+    for fn in sides.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in sides}
+    for _ in range(rounds):  # alternate the sides
+        for k, fn in sides.items():
+            ms[k].append(timed(fn, steps))
+
+    # the kernels of one LARS / LAMB step, each alone over the whole buffer
+    P = len(f.params)
+    parts, sums, q = lamb._unit_parts, lamb._sums, lamb._q
+    hl, hm = lars.param_groups[0], lamb.param_groups[0]
+    b1, b2 = hm["betas"]
+    kernels = {
+        "seg_sqnorm_units (p, g)": (lambda: ops.seg_sqnorm_units_(f.data, parts[0], f.grad, parts[1]),
+                                    8 * n + 16 * units),
+        "seg_sqnorm_reduce (2 x P blocks)": (lambda: ops.seg_sqnorm_reduce_(parts, lamb.owned_units, sums),
+                                             16 * units),
+        "lars_trust": (lambda: ops.lars_trust_(sums, lars.excluded, q, lars.state, hl["trust_coefficient"],
+                                               hl["weight_decay"], hl["eps"]), 21 * P),
+        "lars_flat": (lambda: ops.lars_flat_(f.data, f.grad, lars.momentum_buf, f.bf16, lars.state, lars.unit_param,
+                                             lars.excluded, q, 0, hl["momentum"], hl["weight_decay"]), 22 * n),
+        "lamb_moments": (lambda: ops.lamb_moments_(f.data, f.grad, lamb.exp_avg, lamb.exp_avg_sq, lamb.state,
+                                                   lamb.unit_param, lamb.excluded, 0, parts[0], parts[1], b1, b2,
+                                                   hm["eps"], hm["weight_decay"]), 24 * n + 16 * units),
+        "lamb_apply": (lambda: ops.lamb_apply_(f.data, lamb.exp_avg, lamb.exp_avg_sq, f.bf16, lamb.state,
+                                               lamb.unit_param, lamb.excluded, q, 0, b1, b2, hm["eps"],
+                                               hm["weight_decay"]), 18 * n),
+        "refresh_transposed (step tail)": (f.refresh_transposed, 0),
+    }
+    for fn, _ in kernels.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    kms = {k: [] for k in kernels}
+    for _ in range(rounds):
+        for k, (fn, _) in kernels.items():
+            kms[k].append(timed(fn, steps))
+    units_of = [int(b - a) for a, b in lamb.owned_units.tolist()]
+    return {"model": name, "flat_numel": n, "tensors": P, "units": units, "largest_parameter_units": max(units_of),
+            "steps_per_measurement": steps, "rounds": rounds, "results": _rows(ms, nbytes),
+            "kernels": _rows(kms, {k: b for k, (_, b) in kernels.items()})}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="vitb16,resnet50")
@@ -94,11 +179,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--suite", default="adamw", choices=["adamw", "layerwise"])
     a = ap.parse_args()
     if a.steps < 100:
         ap.error("--steps must be at least 100")
     out = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "hip": torch.version.hip,
-           "models": [bench_model(m, a.steps, a.rounds, a.warmup) for m in a.models.split(",")]}
+           "suite": a.suite,
+           "models": [(bench_layerwise if a.suite == "layerwise" else bench_model)(m, a.steps, a.rounds, a.warmup)
+                      for m in a.models.split(",")]}
     line = json.dumps(out)
     print(line)
     if a.out:
