@@ -829,21 +829,64 @@ __device__ __forceinline__ int tr_swz(int k) {
 // fused bias-gradient column sums (Linear layers only).  Both are compile-time so that neither the
 // gather bookkeeping nor the colsum accumulators occupy registers in the variants that do not use
 // them (the conv variant fits 128 VGPRs and runs 4 blocks per CU).
+//
+// STAGES 1: one 64-row LDS tile, load -> vmcnt(0) -> barrier -> MFMA -> barrier per k-step; only the
+// CU's other resident blocks hide the memory latency.
+// STAGES 2: a ring of S slots of ONE MFMA k-chunk (32 reduction rows) each, the loads S - 1 slots
+// ahead.  A slot step is: counted s_waitcnt vmcnt (the loads younger than the
+// consumed slot stay in flight, never 0 in the loop), one raw s_barrier (publishes the slot and
+// frees the one consumed a step ago), the issue into that freed slot, the MFMAs of the current
+// slot.  Every issue is the same number of load instructions per thread (rows past the split's end
+// go to the out-of-range offset and zero-fill), which makes the count a compile-time constant.  The
+// fragment reads are inline asm: an LDS read hipcc can see while LDS-DMA loads are outstanding gets
+// a vmcnt(0) in front of it (conv_panel.hip).  Each accumulator sees the same 32-row chunks in the
+// same order as with STAGES 1, so the two are bit-identical.
+// S = 4, but 3 for the 128x128 tile: its four slots (64 KB) would hold a CU to 2 blocks, hipcc then
+// drops the 3-blocks launch bound as unreachable and schedules into ~200 VGPRs; three slots (48 KB)
+// keep the one-stage loop's 3 blocks per CU and its 168-VGPR budget.
+constexpr int kTnRingRows = 32;
+template <int BM, int BN>
+constexpr int tn_ring_slots() {
+  return BM + BN >= 256 ? 3 : 4;
+}
+
+template <int BM, int BN, int STAGES, int MODE, bool CS>
+constexpr int tn_blocks_per_cu() {
+  constexpr int one = MODE == 1 && !CS ? kTnConvBlocksPerCu : kTnBlocksPerCu;
+  static_assert(STAGES == 1 || 160 * 1024 / (tn_ring_slots<BM, BN>() * kTnRingRows * (BM + BN) * 2 + 64) >= one,
+                "the ring's LDS must leave the launch bound's blocks resident in a CU's 160 KB");
+  return one;
+}
+
+template <int N>
+__device__ __forceinline__ void tn_vmwait() {
+  static_assert(N > 0 && N <= 63, "counted wait: vmcnt holds 6 bits, and 0 would drain the ring");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+typedef uint32_t tn_u32x2 __attribute__((ext_vector_type(2)));
+
 template <int BM, int BN, int STAGES, int MODE = 1, bool CS = false, bool NOL = false, bool CSB = false>
-__global__ __launch_bounds__(256, STAGES == 1 ? (MODE == 1 && !CS ? kTnConvBlocksPerCu : kTnBlocksPerCu) : 2)
+__global__ __launch_bounds__(256, (tn_blocks_per_cu<BM, BN, STAGES, MODE, CS>()))
 void tn_kernel(TNArgs a) {
-  static_assert(!CSB || (STAGES == 1 && !CS && !NOL), "folded BN backward: the plain one-stage variant");
+  static_assert(STAGES == 1 || STAGES == 2, "one-stage loop or the slot ring");
+  static_assert(!CSB || (!CS && !NOL), "folded BN backward: the plain variants");
   static_assert(!NOL || (MODE == 1 && STAGES == 1 && !CS), "normalize-on-load: conv weight gradients");
+  constexpr bool RING = STAGES == 2;
+  constexpr int KS = RING ? kTnRingRows : BK;        // reduction rows per load issue (LDS buffer)
+  constexpr int NBUF = RING ? tn_ring_slots<BM, BN>() : 1;
   constexpr int WM = BM / 2, WN = BN / 2;
   constexpr int MI = WM / 16, NJ = WN / 16;
   constexpr int AU = BM / 4, BU = BN / 4;            // 8-byte units per LDS row
   constexpr int ACPR = BM / 8, BCPR = BN / 8;        // 16-byte chunks per row
-  constexpr int A_CH = BK * ACPR / 256, B_CH = BK * BCPR / 256;
+  constexpr int A_CH = KS * ACPR / 256, B_CH = KS * BCPR / 256;
   constexpr int A_RSTEP = 256 / ACPR, B_RSTEP = 256 / BCPR;
   constexpr int A_RPI = 64 / ACPR, B_RPI = 64 / BCPR;  // LDS rows per wave-instruction
-  __shared__ __attribute__((aligned(16))) uint2 smem[STAGES * BK * (AU + BU)];
-  uint2* As = smem;                        // [STAGES][BK][AU]
-  uint2* Bs = smem + STAGES * BK * AU;     // [STAGES][BK][BU]
+  static_assert(A_CH >= 1 && B_CH >= 1 && A_CH * A_RSTEP == KS && B_CH * B_RSTEP == KS, "whole passes per issue");
+  // ONE LDS array (a second object can make hipcc drain vmcnt before LDS accesses)
+  __shared__ __attribute__((aligned(16))) uint2 smem[NBUF * KS * (AU + BU)];
+  uint2* As = smem;                        // [NBUF][KS][AU]
+  uint2* Bs = smem + NBUF * KS * AU;       // [NBUF][KS][BU]
 
   const int nbn = (a.N + BN - 1) / BN;
   // 1-D grid of tiles x splits, XCD-aware: each XCD owns a contiguous run of (split, tile) work
@@ -890,7 +933,7 @@ void tn_kernel(TNArgs a) {
     }
   }
 
-  // ---- per-thread B rows (mode 1): output pixel (img, p, q) of reduction row k, advanced by BK
+  // ---- per-thread B rows (mode 1): output pixel (img, p, q) of reduction row k, advanced by KS
   int b_img[B_CH], b_p[B_CH], b_q[B_CH];
 #pragma unroll
   for (int i = 0; i < B_CH; ++i) {
@@ -904,8 +947,8 @@ void tn_kernel(TNArgs a) {
       b_img[i] = b_p[i] = b_q[i] = 0;
     }
   }
-  // per-step carry deltas for +BK pixels
-  const int dq = BK % Q, dp = (BK / Q) % P, dimg = BK / (P * Q);
+  // per-issue carry deltas for +KS pixels
+  const int dq = KS % Q, dp = (KS / Q) % P, dimg = KS / (P * Q);
 
   // folded BN backward: a block's rows lie wholly in dz (A) or in c (A2, rows m - msplit)
   const bool a_second = CSB && a.msplit && m0 >= a.msplit;
@@ -926,7 +969,7 @@ void tn_kernel(TNArgs a) {
       const bool ok = k < kend && a_m < a.M;
       const uint32_t vo = ok ? (uint32_t)(k * (a_second ? a.lda2 : a.lda) + a_mo) * 2u : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsA, LDS_PTR(void, &As[(buf * BK + A_RSTEP * i + wid * A_RPI) * AU]), 16, vo, 0, 0, 0);
+          rsA, LDS_PTR(void, &As[(buf * KS + A_RSTEP * i + wid * A_RPI) * AU]), 16, vo, 0, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < B_CH; ++i) {
@@ -939,14 +982,14 @@ void tn_kernel(TNArgs a) {
         if (k < kend && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W)
           vo = (b_n < a.N) ? (uint32_t)((((b_img[i] * H + ih) * W + iw) * Cs) + c0) * 2u : OOB;
         b_okm |= (vo != OOB ? 1u : 0u) << i;
-        // advance this row by BK output pixels
+        // advance this row by KS output pixels
         int q = b_q[i] + dq, p = b_p[i] + dp, img = b_img[i] + dimg;
         if (q >= Q) { q -= Q; ++p; }
         if (p >= P) { p -= P; ++img; }
         b_q[i] = q; b_p[i] = p; b_img[i] = img;
       }
       __builtin_amdgcn_raw_ptr_buffer_load_lds(
-          rsB, LDS_PTR(void, &Bs[(buf * BK + B_RSTEP * i + wid * B_RPI) * BU]), 16, vo, 0, 0, 0);
+          rsB, LDS_PTR(void, &Bs[(buf * KS + B_RSTEP * i + wid * B_RPI) * BU]), 16, vo, 0, 0, 0);
     }
   };
 
@@ -971,6 +1014,24 @@ void tn_kernel(TNArgs a) {
   f32x4 acc_sb[CSB ? NJ : 1];
 #pragma unroll
   for (int j = 0; j < (CSB ? NJ : 1); ++j) acc_sb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // one 32-row chunk's MFMAs (shared by both loops: same order, same operands)
+  auto mma_chunk = [&](const bf16x8 (&af)[MI], const bf16x8 (&bfr)[NJ]) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    if constexpr (CS) {
+      if (do_cs)
+#pragma unroll
+      for (int i = 0; i < MI; ++i) acc_cs[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], ones, acc_cs[i], 0, 0, 0);
+    }
+    if constexpr (CSB) {
+      if (do_csb)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc_sb[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bfr[j], acc_sb[j], 0, 0, 0);
+    }
+  };
   auto compute = [&](int cur) {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
@@ -993,22 +1054,51 @@ void tn_kernel(TNArgs a) {
         short v8 __attribute__((ext_vector_type(8))) = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         bfr[j] = __builtin_bit_cast(bf16x8, v8);
       }
-#pragma unroll
-      for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-      if constexpr (CS) {
-        if (do_cs)
-#pragma unroll
-        for (int i = 0; i < MI; ++i) acc_cs[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], ones, acc_cs[i], 0, 0, 0);
-      }
-      if constexpr (CSB) {
-        if (do_csb)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc_sb[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bfr[j], acc_sb[j], 0, 0, 0);
-      }
+      mma_chunk(af, bfr);
     }
+  };
+
+  // ring: this lane's fragment byte addresses within slot 0 (rows k1 = 8g + q4 and k1 + 4: the same
+  // swizzle, so the second read is the first plus an immediate offset of 4 rows)
+  uint32_t fa[RING ? MI : 1], fb[RING ? NJ : 1];
+  if constexpr (RING) {
+    const int k1 = 8 * g + q4;
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+      fa[i] = (uint32_t)(uintptr_t)LDS_PTR(void, &As[k1 * AU + (((wm * WM + 16 * i) / 4 + p4) ^ tr_swz<AU>(k1))]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      fb[j] = (uint32_t)(uintptr_t)LDS_PTR(void, &Bs[k1 * BU + (((wn * WN + 16 * j) / 4 + p4) ^ tr_swz<BU>(k1))]);
+  }
+  // the slot's fragment reads, opaque to the compiler, their wait, then the chunk's MFMAs; the empty
+  // asm after the wait ties every fragment to it, so no MFMA can be scheduled ahead of the data
+  auto compute_slot = [&](int cur) {
+    tn_u32x2 alo[MI], ahi[MI], blo[NJ], bhi[NJ];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+      asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
+                   : "=&v"(alo[i]), "=&v"(ahi[i])
+                   : "v"(fa[RING ? i : 0] + (uint32_t)(cur * KS * AU * 8)), "n"(4 * AU * 8)
+                   : "memory");
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+      asm volatile("ds_read_b64_tr_b16 %0, %2\n\tds_read_b64_tr_b16 %1, %2 offset:%3"
+                   : "=&v"(blo[j]), "=&v"(bhi[j])
+                   : "v"(fb[RING ? j : 0] + (uint32_t)(cur * KS * BU * 8)), "n"(4 * BU * 8)
+                   : "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    bf16x8 af[MI], bfr[NJ];
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+      asm volatile("" : "+v"(alo[i]), "+v"(ahi[i]));
+      af[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(alo[i], ahi[i], 0, 1, 2, 3));
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      asm volatile("" : "+v"(blo[j]), "+v"(bhi[j]));
+      bfr[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(blo[j], bhi[j], 0, 1, 2, 3));
+    }
+    mma_chunk(af, bfr);
   };
 
   const int nk = (kend - kbeg + BK - 1) / BK;
@@ -1033,16 +1123,26 @@ void tn_kernel(TNArgs a) {
       __syncthreads();
     }
   } else {
-    issue_loads(kbeg, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nk) issue_loads(kbeg + (kt + 1) * BK, cur ^ 1);
-      compute(cur);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
+    constexpr int S = NBUF;
+    static_assert(S >= 3, "at least one slot in flight behind the wait");
+    constexpr int LPS = A_CH + B_CH;  // load instructions per thread and slot, always issued
+    // two slots per 64-row k-step, a wholly out-of-range last one included: the chunk sequence of
+    // the one-stage loop exactly
+    const int ns = 2 * nk;
+#pragma unroll
+    for (int s = 0; s < S - 1; ++s) issue_loads(kbeg + s * KS, s);
+    int cur = 0, prev = S - 1;  // buffers of slot t and of slot t - 1 (= that of slot t + S - 1)
+    for (int t = 0; t < ns; ++t) {
+      tn_vmwait<(S - 2) * LPS>();  // slots t + 1 .. t + S - 2 stay in flight; this thread's part of slot t is in LDS
+      // everyone's part of slot t is in LDS, and everyone's fragment reads of slot t - 1 have
+      // returned (lgkmcnt(0) before its MFMAs): its buffer is free for slot t + S - 1
+      asm volatile("s_barrier" ::: "memory");
+      issue_loads(kbeg + (t + S - 1) * KS, prev);
+      compute_slot(cur);
+      prev = cur;
+      cur = cur + 1 == S ? 0 : cur + 1;
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's zero-fill loads, before LDS is reused or freed
   }
 
   // bias gradient first (the split-K epilogues below may return early): every column of the
@@ -1072,7 +1172,7 @@ void tn_kernel(TNArgs a) {
     // split-K: this block's partial tile goes to its own slab in fragment order -- every store is one
     // fully coalesced 1 KB wave-instruction (64 lanes x float4) -- and tn_splitk_reduce_kernel sums
     // the splits into C: deterministic, and no fp32 atomics (~1.3 TB/s chip-wide) on the hot path
-    if (STAGES == 1 && a.cnt) {  // GLDS (default) slab variants only
+    if (a.cnt) {  // slab variants with direct-to-LDS only (launch_tn), one-stage or ring
       // one launch: fence-free hand-off to the last-arriving split of the tile (as nt_kernel's
       // SPLIT 3): sc1 partial stores, wait, barrier, one arrival count; the last arriver sums the
       // partials in split order from 0 -- what tn_splitk_reduce_kernel does for fewer than 8
@@ -1728,15 +1828,18 @@ static bool tn_slabs_on() {
   return g_tn_slabs != 0;
 }
 
-// TN k-loop depth with direct-to-LDS loads: 1 = load, wait, compute per k-step (default); 2 = the
-// next k-step's loads in flight under the current one's MFMAs (MI355X_DP_TN_STAGES=2, A/B)
-static int g_tn_stages = -1;
-static int tn_stages() {
+// TN k-loop with direct-to-LDS loads: 1 = load, wait, compute per 64-row k-step; 2 = the ring of
+// 32-row slots with counted waits (tn_kernel); both give the same bits.  MI355X_DP_TN_STAGES=1|2 or
+// mi_set_tn_stages force one for every launch.  Default by operand mode (profiles/tn_ring.md): the
+// conv weight gradients take the ring (ResNet-50 bs256 +1.0 %, ResNet-152 +1.0 %), the Linear ones
+// keep the one-stage loop (ViT-B/16 -2.7 % with the ring).
+static int g_tn_stages = -1;  // -1 = environment not read yet, 0 = the default by mode, 1 / 2 = forced
+static int tn_stages(int mode) {
   if (g_tn_stages < 0) {
     const char* e = std::getenv("MI355X_DP_TN_STAGES");
-    g_tn_stages = (e && e[0] == '2') ? 2 : 1;
+    g_tn_stages = (e && e[0] == '2') ? 2 : (e && e[0] == '1') ? 1 : 0;
   }
-  return g_tn_stages;
+  return g_tn_stages ? g_tn_stages : (mode == 1 ? 2 : 1);
 }
 
 template <int BM, int BN>
@@ -1759,14 +1862,17 @@ hipError_t launch_tn(TNArgs& a, hipStream_t st, int target_blocks) {
     a.ws = splitk_workspace((size_t)tiles * splits * BM * BN, st);
   // fewer than 8 splits: the reduce is one split group (in-order sum), which the last-arriving
   // split runs itself -- no reduce launch; more splits keep the chip-wide reduce kernel
-  const int st_n = glds_on() ? tn_stages() : 2;
-  if (a.ws && splits < 8 && tiles <= SPLITK_COUNTERS && st_n == 1 && tn_split_fused() && !a.nol_scale)
+  // the one-stage loop is the fallback without direct-to-LDS (no last-arriver epilogue there)
+  const int st_n = glds_on() ? tn_stages(a.mode) : 1;
+  if (a.ws && splits < 8 && tiles <= SPLITK_COUNTERS && glds_on() && tn_split_fused() && !a.nol_scale)
     a.cnt = splitk_counters(st);
   if (a.nol_scale) {
-    if (a.mode != 1 || st_n != 1 || a.cnt) return hipErrorNotSupported;
+    // normalize-on-load rewrites its LDS tile in place: the one-stage loop, whatever is selected
+    if (a.mode != 1 || !glds_on() || a.cnt) return hipErrorNotSupported;
     hipLaunchKernelGGL((tn_kernel<BM, BN, 1, 1, false, true>), dim3(tiles * splits), dim3(256), 0, st, a);
   } else if (a.mode == 1 && a.bsum) {  // folded BN backward (mi_conv2d_wgrad_fbb)
-    hipLaunchKernelGGL((tn_kernel<BM, BN, 1, 1, false, false, true>), dim3(tiles * splits), dim3(256), 0, st, a);
+    if (st_n == 1) hipLaunchKernelGGL((tn_kernel<BM, BN, 1, 1, false, false, true>), dim3(tiles * splits), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((tn_kernel<BM, BN, 2, 1, false, false, true>), dim3(tiles * splits), dim3(256), 0, st, a);
   } else if (a.mode == 1) {
     if (st_n == 1) hipLaunchKernelGGL((tn_kernel<BM, BN, 1, 1, false>), dim3(tiles * splits), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((tn_kernel<BM, BN, 2, 1, false>), dim3(tiles * splits), dim3(256), 0, st, a);
@@ -1870,6 +1976,12 @@ MI_API int mi_set_glds(int on) {
 // NT split-K reduction: 1 = fused last-arriver launch (default), 0 = partials + reduce launch (tests).
 MI_API int mi_set_tn_split_fused(int on) {
   g_tn_split_fused = on ? 1 : 0;
+  return 0;
+}
+// TN k-loop for every launch: 1 = one-stage, 2 = the slot ring, anything else = back to the
+// environment / the default by operand mode.
+MI_API int mi_set_tn_stages(int stages) {
+  g_tn_stages = (stages == 1 || stages == 2) ? stages : -1;
   return 0;
 }
 MI_API int mi_set_nt_split_fused(int on) {
