@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--n-test", type=int, default=10000)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--mixup-alpha", type=float, default=0.0, help="Mixup Beta(alpha, alpha); 0 = off")
+    ap.add_argument("--cutmix-alpha", type=float, default=0.0, help="CutMix Beta(alpha, alpha); 0 = off")
     a = ap.parse_args()
     t_job = time.time()
     import torch
@@ -58,7 +61,7 @@ def main():
     if world > 1:
         dist.init_process_group("nccl", device_id=dev)
     from mi355x_dp.models import get_model
-    from mi355x_dp.ops import augment, cross_entropy
+    from mi355x_dp.ops import MixedTarget, augment, augment_mix, cross_entropy
     from mi355x_dp.parallel import DataParallel, FlatSGD
 
     xtr, ytr, xte, yte = load_data(a.data, a.n_train, a.n_test, a.seed)
@@ -82,9 +85,20 @@ def main():
     yb = torch.empty((B,), dtype=torch.long, device=dev)
     x = torch.empty((B, 8, 32, 32), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
 
+    # Mixup / CutMix: the mixing parameters are drawn on the host per step, the mixing itself and the
+    # pair target (static buffers, rewritten before every replay) come out of the augmentation pass
+    mixer = target = None
+    if a.mixup_alpha > 0 or a.cutmix_alpha > 0:
+        from mi355x_dp.data.mix import BatchMixer
+        mixer = BatchMixer(a.mixup_alpha, a.cutmix_alpha, seed=a.seed, rank=rank, device=dev)
+        target = MixedTarget(torch.empty_like(yb), torch.empty_like(yb), torch.ones(B, device=dev))
+
     def core():
         engine.zero_grad()
-        loss = cross_entropy(engine(x), yb)
+        if mixer is not None:
+            loss = cross_entropy(engine(x), target, label_smoothing=a.label_smoothing)
+        else:  # label_smoothing 0 (the default): the hard-label kernels, as before
+            loss = cross_entropy(engine(x), yb, label_smoothing=a.label_smoothing)
         loss.backward()
         opt.step()
         return loss
@@ -95,7 +109,11 @@ def main():
         nonlocal graphed, step_no
         torch.index_select(imgs, 0, idx, out=u8)
         torch.index_select(labels, 0, idx, out=yb)
-        augment(u8, 8, MEAN, STD, pad=4, flip=True, seed=a.seed * 1000003 + step_no, out=x)
+        if mixer is not None:
+            augment_mix(u8, yb, 8, MEAN, STD, mixer.params(step_no, B, 32, 32), pad=4, flip=True,
+                        seed=a.seed * 1000003 + step_no, out=x, target=target)
+        else:
+            augment(u8, 8, MEAN, STD, pad=4, flip=True, seed=a.seed * 1000003 + step_no, out=x)
         step_no += 1
         if a.no_graph or step_no == 1:
             return core()

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -605,11 +606,124 @@ class _CrossEntropy(torch.autograd.Function):
         return dl.to(ctx.in_dtype), None
 
 
-def cross_entropy(logits, target):
-    """Mean-reduced cross entropy (log-softmax + NLL) fused fwd/bwd."""
+class MixedTarget(NamedTuple):
+    """Mixup / CutMix target: row n is ``lam[n]`` of class ``y_a[n]`` and ``1 - lam[n]`` of class
+    ``y_b[n]``.  ``y_a`` / ``y_b`` int64 [N], ``lam`` fp32 [N] on the logits' device (a device tensor,
+    so a loss captured in a HIP graph sees the new values on every replay)."""
+    y_a: torch.Tensor
+    y_b: torch.Tensor
+    lam: torch.Tensor
+
+    def dense(self, num_classes, dtype=torch.float32):
+        """The equivalent [N, C] probability target (reference / CPU path; the kernels never build it)."""
+        lam = self.lam.to(dtype).unsqueeze(1)
+        return lam * F.one_hot(self.y_a, num_classes).to(dtype) + (1 - lam) * F.one_hot(self.y_b, num_classes).to(dtype)
+
+
+class _CrossEntropyPair(torch.autograd.Function):
+    """Pair target (y_a, y_b, lam) with label smoothing; ``lam is None``: hard labels (y_a is y_b)."""
+
+    @staticmethod
+    def forward(ctx, logits, y_a, y_b, lam, eps):
+        lg = logits.float().contiguous()
+        N, ncls = lg.shape
+        ws = torch.empty(2 * N, dtype=torch.float32, device=lg.device)  # [lse rows | per-row losses]
+        loss = torch.empty((), dtype=torch.float32, device=lg.device)
+        _lib.call("mi_ce_pair_fwd", ptr(lg), ptr(y_a), ptr(y_b), ptr(lam), ptr(ws),
+                  ptr(loss), N, ncls, ncls, eps, stream_of(lg))
+        ctx.save_for_backward(lg, y_a, y_b, ws, *(() if lam is None else (lam,)))
+        ctx.in_dtype, ctx.eps = logits.dtype, eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        lg, y_a, y_b, ws, *rest = ctx.saved_tensors
+        lam = rest[0] if rest else None
+        N, ncls = lg.shape
+        g = gout.float().contiguous().reshape(1)
+        f32 = ctx.in_dtype == torch.float32  # the gradient in the logits' dtype: no autograd cast launch
+        dl = torch.empty((N, ncls), dtype=torch.float32 if f32 else BF16, device=lg.device)
+        _lib.call("mi_ce_pair_bwd", ptr(lg), ptr(y_a), ptr(y_b), ptr(lam), ptr(ws),
+                  ptr(g), ptr(dl), N, ncls, ncls, ncls, ctx.eps, int(f32), stream_of(lg))
+        return dl.to(ctx.in_dtype), None, None, None, None
+
+
+class _CrossEntropyDense(torch.autograd.Function):
+    """Dense [N, C] probability targets (fp32 or bf16; rows need not sum to one) with label smoothing."""
+
+    @staticmethod
+    def forward(ctx, logits, target, eps):
+        lg = logits.float().contiguous()
+        N, ncls = lg.shape
+        tgt = target.contiguous()
+        ws = torch.empty(3 * N, dtype=torch.float32, device=lg.device)  # [lse rows | per-row losses | sum q]
+        loss = torch.empty((), dtype=torch.float32, device=lg.device)
+        _lib.call("mi_ce_dense_fwd", ptr(lg), ptr(tgt), int(tgt.dtype == BF16), ptr(ws), ptr(loss), N, ncls, ncls,
+                  ncls, eps, stream_of(lg))
+        ctx.save_for_backward(lg, tgt, ws)
+        ctx.in_dtype, ctx.eps = logits.dtype, eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        lg, tgt, ws = ctx.saved_tensors
+        N, ncls = lg.shape
+        g = gout.float().contiguous().reshape(1)
+        f32 = ctx.in_dtype == torch.float32
+        dl = torch.empty((N, ncls), dtype=torch.float32 if f32 else BF16, device=lg.device)
+        _lib.call("mi_ce_dense_bwd", ptr(lg), ptr(tgt), int(tgt.dtype == BF16), ptr(ws), ptr(g), ptr(dl), N, ncls,
+                  ncls, ncls, ncls, ctx.eps, int(f32), stream_of(lg))
+        return dl.to(ctx.in_dtype), None, None
+
+
+def _index_target(t, N, dev, what):
+    if t.dtype != torch.int64 or t.shape != (N,) or t.device != dev:
+        raise ValueError(f"cross_entropy: {what} must be an int64 [{N}] tensor on {dev}")
+    return t.contiguous()
+
+
+def cross_entropy(logits, target, label_smoothing=0.0):
+    """Mean-reduced cross entropy (log-softmax + NLL) fused fwd/bwd, ``F.cross_entropy`` semantics.
+
+    ``target``: int64 [N] class indices, a ``MixedTarget(y_a, y_b, lam)`` (Mixup / CutMix; [N, C] is
+    never materialised) or a floating-point [N, C] probability tensor (fp32 or bf16).  Smoothing acts
+    on probability targets as ``q = (1 - eps) * t + eps / C``."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"label_smoothing must be in [0, 1], got {label_smoothing}")
+    if logits.dim() != 2:
+        raise ValueError("cross_entropy expects [N, C] logits")
+    N, ncls = logits.shape
+    mixed = isinstance(target, MixedTarget)
+    dense = not mixed and target.is_floating_point()
     if not logits.is_cuda:
-        return F.cross_entropy(logits.float(), target)
-    return _CrossEntropy.apply(logits, target)
+        if not mixed and not dense and eps == 0.0:
+            return F.cross_entropy(logits.float(), target)
+        if mixed:
+            t = target.dense(ncls)
+        elif dense:
+            t = target.float()
+        else:
+            t = F.one_hot(target, ncls).float()
+        return F.cross_entropy(logits.float(), t, label_smoothing=eps)
+    dev = logits.device
+    if mixed:
+        y_a = _index_target(target.y_a, N, dev, "MixedTarget.y_a")
+        y_b = _index_target(target.y_b, N, dev, "MixedTarget.y_b")
+        lam = target.lam
+        if lam.dtype != torch.float32 or lam.shape != (N,) or lam.device != dev:
+            raise ValueError(f"cross_entropy: MixedTarget.lam must be an fp32 [{N}] tensor on {dev}")
+        return _CrossEntropyPair.apply(logits, y_a, y_b, lam.contiguous(), eps)
+    if dense:
+        if target.shape != (N, ncls) or target.device != dev:
+            raise ValueError(f"cross_entropy: dense targets must be [{N}, {ncls}] on {dev}")
+        if target.dtype not in (torch.float32, BF16):
+            target = target.float()
+        return _CrossEntropyDense.apply(logits, target, eps)
+    if eps == 0.0:
+        return _CrossEntropy.apply(logits, target)  # today's hard-label kernels, unchanged
+    y = _index_target(target.to(torch.int64), N, dev, "target")
+    return _CrossEntropyPair.apply(logits, y, y, None, eps)
 
 
 # ================================================================= optimizer
@@ -993,3 +1107,70 @@ def augment(images_u8, out_channels, mean, std, pad=4, flip=True, seed=0, out=No
     _lib.call("mi_augment", ptr(images_u8.contiguous()), ptr(out), N, H, W, C, out_channels, int(pad), int(flip),
               seed & 0xFFFFFFFF, ptr(mean_t), ptr(stdinv_t), stream_of(images_u8))
     return out
+
+
+def augment_mix(images_u8, labels, out_channels, mean, std, params, pad=4, flip=True, seed=0, out=None, target=None):
+    """``augment`` with Mixup / CutMix folded into the same uint8 -> bf16 pass; returns
+    ``(x, MixedTarget)``.
+
+    ``params`` carries the per-sample, device-resident mixing parameters (``data.mix.BatchMixer``):
+    ``partner`` int32 [N], ``lam`` fp32 [N], ``box`` int32 [N, 4] = (y0, y1, x0, x1) in output
+    coordinates.  An empty box blends ``lam * a + (1 - lam) * b`` in fp32 (Mixup); a non-empty box
+    takes the partner inside it and the image outside (CutMix).  Image and partner each keep the
+    crop / flip that ``augment`` gives them for this ``seed``.  The kernel also writes the target:
+    ``y_a = labels``, ``y_b = labels[partner]`` and the label-side lam (CutMix: 1 - clipped box
+    area / (H * W)).  ``out`` / ``target``: static buffers to write into (the inputs of a captured
+    HIP-graph step)."""
+    N, H, W, C = images_u8.shape
+    dev = images_u8.device
+    if not images_u8.is_cuda:
+        x = augment(images_u8, out_channels, mean, std, pad=pad, flip=flip, seed=seed)
+        partner, lam = params.partner.long(), params.lam.float().clone()
+        ok = (partner >= 0) & (partner < N)
+        partner = torch.where(ok, partner, torch.arange(N))
+        lam[~ok] = 1.0
+        box = params.box.long()
+        y0, y1 = box[:, 0].clamp(0, H), box[:, 1].clamp(0, H)
+        x0, x1 = box[:, 2].clamp(0, W), box[:, 3].clamp(0, W)
+        cut = ok & (y1 > y0) & (x1 > x0)
+        hh, ww = torch.arange(H).view(1, H, 1), torch.arange(W).view(1, 1, W)
+        inbox = (cut.view(N, 1, 1) & (hh >= y0.view(N, 1, 1)) & (hh < y1.view(N, 1, 1))
+                 & (ww >= x0.view(N, 1, 1)) & (ww < x1.view(N, 1, 1))).unsqueeze(1)
+        lam_px = torch.where(cut, torch.ones_like(lam), lam).view(N, 1, 1, 1)
+        xb = x[partner]
+        x = torch.where(inbox, xb, lam_px * x + (1 - lam_px) * xb)
+        lam = torch.where(cut, 1.0 - ((y1 - y0) * (x1 - x0)).float() / float(H * W), lam)
+        return x, MixedTarget(labels.long(), labels.long()[partner], lam)
+    if labels.dtype != torch.int64 or labels.shape != (N,) or labels.device != dev:
+        raise ValueError(f"augment_mix: labels must be an int64 [{N}] tensor on {dev}")
+    partner, lam, box = params.partner, params.lam, params.box
+    if not (partner.dtype == torch.int32 and partner.shape == (N,) and partner.device == dev
+            and partner.is_contiguous()):
+        raise ValueError(f"augment_mix: params.partner must be a contiguous int32 [{N}] tensor on {dev}")
+    if not (lam.dtype == torch.float32 and lam.shape == (N,) and lam.device == dev and lam.is_contiguous()):
+        raise ValueError(f"augment_mix: params.lam must be a contiguous fp32 [{N}] tensor on {dev}")
+    if not (box.dtype == torch.int32 and box.shape == (N, 4) and box.device == dev and box.is_contiguous()):
+        raise ValueError(f"augment_mix: params.box must be a contiguous int32 [{N}, 4] tensor on {dev}")
+    key = (str(dev), max(out_channels, C), C, tuple(mean), tuple(std))
+    if key not in _AUG_CONST:  # augment's device constants, shared with it
+        mean_t = torch.zeros(max(out_channels, C), dtype=torch.float32, device=dev)
+        stdinv_t = torch.ones(max(out_channels, C), dtype=torch.float32, device=dev)
+        mean_t[:C] = torch.tensor(mean, dtype=torch.float32)
+        stdinv_t[:C] = 1.0 / torch.tensor(std, dtype=torch.float32)
+        _AUG_CONST[key] = (mean_t, stdinv_t)
+    mean_t, stdinv_t = _AUG_CONST[key]
+    if out is None:
+        out = torch.empty((N, out_channels, H, W), dtype=BF16, device=dev, memory_format=CL)
+    elif not (out.shape == (N, out_channels, H, W) and out.dtype == BF16 and out.is_contiguous(memory_format=CL)):
+        raise ValueError("augment_mix(out=...) needs a bf16 channels_last [N, Cout, H, W] tensor")
+    if target is None:
+        target = MixedTarget(torch.empty_like(labels), torch.empty_like(labels),
+                             torch.empty(N, dtype=torch.float32, device=dev))
+    else:
+        for t, dt in ((target.y_a, torch.int64), (target.y_b, torch.int64), (target.lam, torch.float32)):
+            if not (t.dtype == dt and t.shape == (N,) and t.device == dev and t.is_contiguous()):
+                raise ValueError(f"augment_mix(target=...) needs contiguous int64 / int64 / fp32 [{N}] tensors on {dev}")
+    _lib.call("mi_augment_mix", ptr(images_u8.contiguous()), ptr(out), ptr(labels.contiguous()), ptr(partner),
+              ptr(lam), ptr(box), ptr(target.y_a), ptr(target.y_b), ptr(target.lam), N, H, W, C, out_channels,
+              int(pad), int(flip), seed & 0xFFFFFFFF, ptr(mean_t), ptr(stdinv_t), stream_of(images_u8))
+    return out, target
