@@ -28,6 +28,7 @@
 //  * XCD-aware, M-grouped tile order (GROUP_M 8) for L2 reuse of the B panel.
 #include "common.h"
 #include "epilogue.h"
+#include "philox.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -78,6 +79,12 @@ struct G256Args {
   int a2_bytes, khalf_kt;
 };
 
+// DROP kernels: plus the dropout / stochastic-depth masks of the epilogue (philox.h) -- a type of its
+// own, so the other instantiations keep their kernel arguments (and their code) as they are
+struct G256DropArgs : G256Args {
+  DropArgs drop;
+};
+
 // Wave priority: static s_setprio 1 for the second-dispatched half (waves 4-7) before the main loop
 // (MI355X_MICROARCH.md, two waves per SIMD, item 4) -- the guard must be provably wave-uniform
 // (readfirstlane): a plain `if (wid >= 4)` lowers to s_and_saveexec + an UNCONDITIONAL s_setprio,
@@ -100,10 +107,13 @@ __device__ __forceinline__ void phase_barrier() { asm volatile("s_barrier" ::: "
 // SCAT (MODE 0, bf16 out): output row m goes to row 2 (m / Q) W + 2 (m % Q) of C -- the even pixels of a
 // 2H' x 2W' grid: the stride-2 1x1 data gradient of a projection shortcut written straight into the
 // even pixels of dx (Q = a.fQ.d, W = a.W; mi_gemm256_nt_scat2)
-template <int MODE, int WR = 128, bool SCAT = false>
-__global__ __launch_bounds__(512, 1) void gemm256_nt_kernel(G256Args a) {
+// DROP (MODE 0, bf16 out): 1 residual-drop C <- v * m + aux (launched with epi 3, whose aux loads it
+// shares), 2 GELU-drop C <- gelu(v) * m, aux <- gelu'(v) * m (epi 1); m = a.drop's masks at (row, col)
+template <int MODE, int WR = 128, bool SCAT = false, int DROP = 0, class ARGS = G256Args>
+__global__ __launch_bounds__(512, 1) void gemm256_nt_kernel(ARGS a) {
   static_assert(WR == 128 || WR == 112, "256- or 224-row tiles");
   static_assert(!SCAT || MODE == 0, "scattered rows: plain GEMM only");
+  static_assert(DROP == 0 || (MODE == 0 && !SCAT), "drop epilogues: plain GEMM only");
   constexpr int IQ1 = (WR - 64) / 16;  // fragment rows of quadrant row 1
   constexpr int NI = 4 + IQ1;          // accumulator rows per wave
   __shared__ __attribute__((aligned(16))) uint4 smem[2 * 4 * PART_U4];  // 128 KB
@@ -374,6 +384,8 @@ __global__ __launch_bounds__(512, 1) void gemm256_nt_kernel(G256Args a) {
   }
   const int cc = lane & 7;
   const int n = n0 + wn * 64 + cc * 8;
+  DropKey dkey{};
+  if constexpr (DROP != 0) dkey = drop_key(a.drop);
   // plain GEMMs (MODE 0: transformer layers) never carry BN statistics or the BN-backward
   // epilogues: compiled out, their registers go to a deeper batch of epilogue operand loads
   constexpr bool BN_EPI = MODE != 0;
@@ -473,6 +485,11 @@ __global__ __launch_bounds__(512, 1) void gemm256_nt_kernel(G256Args a) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) { s1[q] += f[q]; s2[q] += f[q] * (xv[q] - mu[q]); }
           }
+        } else if constexpr (DROP != 0) {
+          const uint32_t m = (uint32_t)(m0 + wm * WR + mq * 64 + rl);
+          float dm[8];
+          const uint32_t keep = drop_chunk(a.drop, dkey, m, m * (uint32_t)(a.N >> 3) + (uint32_t)(n >> 3), dm);
+          o = DROP == 1 ? drop_residual_v(v, yq[sl][u], dm, keep) : drop_gelu_v(v, a.aux + off, dm, keep);
         } else {
           if (a.epi) o = epilogue_op_v(a.epi, v, a.aux + off, yq[sl][u]);
           if (has_stats) {
@@ -932,6 +949,37 @@ MI_API int mi_gemm256_nt(const void* A, const void* B, void* C, const float* bia
   if (hipError_t e = plan_tail(a, cdiv(K, G_BK), st); e != hipSuccess) return (int)e;
   if (wr == 112) hipLaunchKernelGGL((gemm256_nt_kernel<0, 112>), dim3(grid_of(a)), dim3(512), 0, st, a);
   else hipLaunchKernelGGL((gemm256_nt_kernel<0, 128>), dim3(grid_of(a)), dim3(512), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+// mi_gemm256_nt with a dropped epilogue (philox.h): kind 1 residual-drop C <- (acc + bias) * m + aux,
+// kind 2 GELU-drop C <- gelu(acc + bias) * m, aux <- gelu'(acc + bias) * m.  m = element mask (thr_e,
+// site_e) x row mask (thr_r, site_r, rows_per_sample) drawn from the device state block `state`;
+// thr == 0: that factor is inactive.  bf16 out; never the persistent kernel.
+MI_API int mi_gemm256_nt_drop(const void* A, const void* B, void* C, const float* bias, void* aux, int kind, int M,
+                              int N, int K, int lda, int ldb, int ldc, const void* state, int thr_e, int site_e,
+                              int thr_r, int site_r, int rank, int rows_per_sample, hipStream_t st) {
+  if (K % 8 != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || !aux || M <= 0 || N <= 0 ||
+      (kind != 1 && kind != 2) || (kind == 2 && thr_r))
+    return (int)hipErrorInvalidValue;
+  G256DropArgs a{};
+  if (!drop_args(a.drop, state, thr_e, site_e, thr_r, site_r, rank, rows_per_sample, M, N))
+    return (int)hipErrorInvalidValue;
+  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = bias; a.aux = (bf16_t*)aux;
+  a.epi = kind == 1 ? 3 : 1;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  const int wr = g256_wr(M, N, K, false);
+  a.tiles_m = cdiv(M, 2 * wr); a.tiles_n = cdiv(N, G_BN);
+  a.a_bytes = rsrc_bytes256((int64_t)M * lda);
+  a.b_bytes = rsrc_bytes256((int64_t)N * ldb);
+  if (!a.a_bytes || !a.b_bytes) return (int)hipErrorInvalidValue;
+  if (hipError_t e = plan_tail(a, cdiv(K, G_BK), st); e != hipSuccess) return (int)e;
+  const dim3 grid(grid_of(a)), block(512);
+  using DA = G256DropArgs;
+  if (kind == 1 && wr == 112) hipLaunchKernelGGL((gemm256_nt_kernel<0, 112, false, 1, DA>), grid, block, 0, st, a);
+  else if (kind == 1) hipLaunchKernelGGL((gemm256_nt_kernel<0, 128, false, 1, DA>), grid, block, 0, st, a);
+  else if (wr == 112) hipLaunchKernelGGL((gemm256_nt_kernel<0, 112, false, 2, DA>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((gemm256_nt_kernel<0, 128, false, 2, DA>), grid, block, 0, st, a);
   return (int)hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 //    fp32-atomic variant cost ~1 ms per ResNet-50 step at ~1.3 TB/s of atomics).
 #include "common.h"
 #include "epilogue.h"
+#include "philox.h"
 #include <algorithm>
 #include <array>
 #include <climits>
@@ -105,6 +106,12 @@ struct NTArgs {
   ConvGeom g;
 };
 
+// DROP kernels: plus the dropout / stochastic-depth masks of the epilogue (philox.h) -- a type of its
+// own, so the other instantiations keep their kernel arguments (and their code) as they are
+struct NTDropArgs : NTArgs {
+  DropArgs drop;
+};
+
 struct TNArgs {
   const bf16_t* A;  // [K][M] (row stride lda)
   const bf16_t* B;  // plain [K][N] (ldb) or gathered NHWC input (mode 1)
@@ -185,8 +192,12 @@ constexpr int nt_occupancy() {
 // per-tap gather re-reads every input pixel ~9x through L2; the halo reads it ~(rp+2)/rp x.
 // NOL: 0 off, 1 normalize-on-load of the gathered A operand (conv forward), 2 epi-4 ReLU mask from c
 // (data gradient) -- separate instantiations, so each carries only its own registers
-template <int BM, int BN, int STAGES, bool SMALLC, bool HALO = false, int SPLIT = 0, int NOL = 0>
-__global__ __launch_bounds__(256, (nt_occupancy<BN, STAGES, HALO>())) void nt_kernel(NTArgs a) {
+// DROP (plain GEMM, bf16 out): 1 residual-drop C <- v * m + aux (launched with epi 3, whose aux loads it
+// shares), 2 GELU-drop C <- gelu(v) * m, aux <- gelu'(v) * m (epi 1); m = a.drop's masks at (row, col)
+template <int BM, int BN, int STAGES, bool SMALLC, bool HALO = false, int SPLIT = 0, int NOL = 0, int DROP = 0,
+          class ARGS = NTArgs>
+__global__ __launch_bounds__(256, (nt_occupancy<BN, STAGES, HALO>())) void nt_kernel(ARGS a) {
+  static_assert(DROP == 0 || (STAGES == 1 && !SMALLC && !HALO && SPLIT == 0 && NOL == 0), "drop epilogues: plain tiles");
   static_assert(SPLIT == 0 || (STAGES == 1 && !SMALLC && !HALO), "split-K: single-stage gather/plain tiles only");
   static_assert(NOL == 0 || (STAGES == 1 && !SMALLC && SPLIT == 0), "normalize-on-load: single-stage gather tiles");
   // SPLIT 3: as SPLIT 1, then the last-arriving split of each tile sums all the partial tiles (in
@@ -657,6 +668,8 @@ __global__ __launch_bounds__(256, (nt_occupancy<BN, STAGES, HALO>())) void nt_ke
   constexpr int RPP = 256 / CPR;       // rows per pass
   const int cc = tid % CPR, rr = tid / CPR;
   const int n = n0 + cc * 8;
+  DropKey dkey{};
+  if constexpr (DROP != 0) dkey = drop_key(a.drop);
   float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float mu[8];
   if (a.epi >= 4 && a.stats && n < a.N) {
@@ -685,7 +698,8 @@ __global__ __launch_bounds__(256, (nt_occupancy<BN, STAGES, HALO>())) void nt_ke
   // serialising behind each step's store (the compiler cannot move a load across a store to C).
   constexpr int NSTEP = BM / RPP;
   // (the mask-from-c 128x128 variant loads one operand per step instead of two: half the group)
-  constexpr int EU0 = (NOL == 2 && BN == 128) ? kNtEpiEU / 2 : kNtEpiEU;
+  // (so do the 128x128 drop variants: the Philox state lives beside the group's operands)
+  constexpr int EU0 = ((NOL == 2 || DROP != 0) && BN == 128) ? kNtEpiEU / 2 : kNtEpiEU;
   constexpr int EU = NSTEP < EU0 ? NSTEP : EU0;
   constexpr int NG = NSTEP / EU;
   static_assert(NSTEP % EU == 0, "epilogue groups must tile the row steps");
@@ -770,6 +784,11 @@ __global__ __launch_bounds__(256, (nt_occupancy<BN, STAGES, HALO>())) void nt_ke
 #pragma unroll
           for (int q = 0; q < 8; ++q) { s1[q] += f[q]; s2[q] += f[q] * (xv[q] - mu[q]); }
         }
+      } else if constexpr (DROP != 0) {
+        const uint32_t m = (uint32_t)(m0 + ml);
+        float dm[8];
+        const uint32_t keep = drop_chunk(a.drop, dkey, m, m * (uint32_t)(a.N >> 3) + (uint32_t)(n >> 3), dm);
+        o = DROP == 1 ? drop_residual_v(v, yq[sl][u], dm, keep) : drop_gelu_v(v, a.aux + off, dm, keep);
       } else {
         if (a.epi) o = epilogue_op_v(a.epi, v, a.aux + off, yq[sl][u]);
         if (a.stats) {
@@ -1543,6 +1562,19 @@ hipError_t launch_nt(NTArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((nt_kernel<BM, BN, 2, false>), dim3(grid, classes), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((nt_kernel<BM, BN, 1, false>), dim3(grid, classes), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// plain GEMM with a dropped epilogue (DROP kernels): one single-stage launch, no split-K
+template <int BM, int BN>
+hipError_t launch_nt_drop(NTDropArgs& a, int kind, hipStream_t st) {
+  a.tiles_m = cdiv(a.M, BM);
+  const int grid = a.tiles_m * cdiv(a.N, BN);
+  if (a.a_bytes <= 0 || a.b_bytes <= 0) return hipErrorInvalidValue;
+  if (kind == 1)
+    hipLaunchKernelGGL((nt_kernel<BM, BN, 1, false, false, 0, 0, 1, NTDropArgs>), dim3(grid, 1), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL((nt_kernel<BM, BN, 1, false, false, 0, 0, 2, NTDropArgs>), dim3(grid, 1), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
@@ -2413,6 +2445,38 @@ MI_API int mi_gemm_nt_epi(const void* A, const void* B, void* C, const float* bi
   a.b_bytes = rsrc_bytes((int64_t)N * ldb);
   a.g = make_geom(1, 1, 64, 1, 1, 1, 1, 0);
   return (int)dispatch_nt(a, st);
+}
+
+// mi_gemm_nt_epi with a dropped epilogue (philox.h): kind 1 residual-drop C <- (acc + bias) * m + aux,
+// kind 2 GELU-drop C <- gelu(acc + bias) * m, aux <- gelu'(acc + bias) * m, with m = element mask
+// (thr_e, site_e) x row mask (thr_r, site_r, rows_per_sample) drawn from the device state block
+// `state` ([seed, step]); thr == 0: that factor is inactive.  Routed like mi_gemm_nt_epi.
+extern "C" int mi_gemm256_nt_drop(const void* A, const void* B, void* C, const float* bias, void* aux, int kind, int M,
+                                  int N, int K, int lda, int ldb, int ldc, const void* state, int thr_e, int site_e,
+                                  int thr_r, int site_r, int rank, int rows_per_sample, hipStream_t st);
+MI_API int mi_gemm_nt_epi_drop(const void* A, const void* B, void* C, const float* bias, void* aux, int kind, int M,
+                               int N, int K, int lda, int ldb, int ldc, const void* state, int thr_e, int site_e,
+                               int thr_r, int site_r, int rank, int rows_per_sample, hipStream_t st) {
+  if (K % 8 != 0 || N % 8 != 0 || ldc % 8 != 0 || (kind != 1 && kind != 2) || !aux || (kind == 2 && thr_r) ||
+      M <= 0)
+    return (int)hipErrorInvalidValue;
+  if (use_gemm256(M, N, K) && lda % 8 == 0 && ldb % 8 == 0)
+    return mi_gemm256_nt_drop(A, B, C, bias, aux, kind, M, N, K, lda, ldb, ldc, state, thr_e, site_e, thr_r, site_r,
+                              rank, rows_per_sample, st);
+  NTDropArgs a{};
+  if (!drop_args(a.drop, state, thr_e, site_e, thr_r, site_r, rank, rows_per_sample, M, N))
+    return (int)hipErrorInvalidValue;
+  a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.bias = bias; a.stats = nullptr;
+  a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
+  a.mode = 0; a.out_f32 = 0; a.accumulate = 0; a.aux = (bf16_t*)aux; a.epi = kind == 1 ? 3 : 1;
+  a.a_bytes = rsrc_bytes((int64_t)M * lda);
+  a.b_bytes = rsrc_bytes((int64_t)N * ldb);
+  a.g = make_geom(1, 1, 64, 1, 1, 1, 1, 0);
+  const int ch = nt_choice(M, N);
+  trace_gemm(ch == 2 ? "nt64x64-drop" : (ch == 1 ? "nt128x64-drop" : "nt128x128-drop"), 0, M, N, K, 64, 1, 1, a.epi, 0,
+             cdiv(M, ch == 2 ? 64 : 128) * cdiv(N, ch == 0 ? 128 : 64), 1);
+  if (ch == 2) return (int)launch_nt_drop<64, 64>(a, kind, st);
+  return (int)(ch == 1 ? launch_nt_drop<128, 64>(a, kind, st) : launch_nt_drop<128, 128>(a, kind, st));
 }
 
 // Plain GEMM, "TN": C[M][N] (fp32) += A[K][M]^T * B[K][N].

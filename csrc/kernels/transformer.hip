@@ -3,6 +3,7 @@
 // fp32 statistics / parameters / gradients.  The GEMMs themselves (QKV, projections, MLP with
 // fused GELU and residual epilogues) are the MFMA kernels of gemm_conv.hip.
 #include "common.h"
+#include "philox.h"
 #include <map>
 #include <mutex>
 #include <algorithm>
@@ -301,10 +302,12 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const bf16_t* __restrict_
 // out[n][0][:] = cls + pos[0], out[n][1 + p][:] = patches[n][p][:] + pos[1 + p]: the class-token
 // concatenation and the position-embedding add in one pass (fp32 math, one bf16 rounding).
 // 8 channels per thread; T = tokens (patches + 1), D % 8 == 0.
-__global__ __launch_bounds__(256) void vit_embed_fwd_kernel(const bf16_t* __restrict__ patches,
-                                                            const float* __restrict__ cls,
-                                                            const float* __restrict__ pos, bf16_t* __restrict__ out,
-                                                            int64_t total8, int T, int D) {
+// DROP: the embedding dropout folded in -- the element mask of the [N * T][D] output (philox.h; chunk
+// i of the output is chunk q = i of the mask) multiplies the fp32 sum before its one rounding
+template <bool DROP>
+__device__ __forceinline__ void vit_embed_fwd_body(const bf16_t* __restrict__ patches, const float* __restrict__ cls,
+                                                   const float* __restrict__ pos, bf16_t* __restrict__ out,
+                                                   int64_t total8, int T, int D, const DropArgs* d) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total8) return;
   const int64_t e = i * 8;
@@ -322,7 +325,28 @@ __global__ __launch_bounds__(256) void vit_embed_fwd_kernel(const bf16_t* __rest
   const float4 p0 = *(const float4*)(pos + r), p1 = *(const float4*)(pos + r + 4);
   f[0] += p0.x; f[1] += p0.y; f[2] += p0.z; f[3] += p0.w;
   f[4] += p1.x; f[5] += p1.y; f[6] += p1.z; f[7] += p1.w;
+  if constexpr (DROP) {
+    float m[8];
+    drop_chunk(*d, drop_key(*d), (uint32_t)(n * T + t), (uint32_t)i, m);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) f[q] *= m[q];
+  }
   *(uint4*)(out + e) = pack8(f);
+}
+
+__global__ __launch_bounds__(256) void vit_embed_fwd_kernel(const bf16_t* __restrict__ patches,
+                                                            const float* __restrict__ cls,
+                                                            const float* __restrict__ pos, bf16_t* __restrict__ out,
+                                                            int64_t total8, int T, int D) {
+  vit_embed_fwd_body<false>(patches, cls, pos, out, total8, T, D, nullptr);
+}
+
+__global__ __launch_bounds__(256) void vit_embed_fwd_drop_kernel(const bf16_t* __restrict__ patches,
+                                                                 const float* __restrict__ cls,
+                                                                 const float* __restrict__ pos,
+                                                                 bf16_t* __restrict__ out, int64_t total8, int T, int D,
+                                                                 DropArgs d) {
+  vit_embed_fwd_body<true>(patches, cls, pos, out, total8, T, D, &d);
 }
 
 // Patchify for a stride = kernel = p patch embedding: x NHWC [N][H][W][Cs] bf16 -> out [N * (H/p) *
@@ -360,9 +384,12 @@ __global__ __launch_bounds__(256) void vit_patchify_kernel(const bf16_t* __restr
 // per image-group partial sums part[g][t * D + c] = sum over the group's images of dout[n][t][c]
 // (fixed order).  Block (x, g): 256 threads x 8 channels of the T * D positions, images
 // [g * per_g, (g + 1) * per_g).
-__global__ __launch_bounds__(256) void vit_embed_bwd_kernel(const bf16_t* __restrict__ dout,
-                                                            bf16_t* __restrict__ dpatches, float* __restrict__ part,
-                                                            int N, int T, int D, int per_g) {
+// DROP: dout is first multiplied by the forward's element mask (redrawn) and rounded to bf16, the
+// gradient of the undropped embedding that both the patches and the sums see
+template <bool DROP>
+__device__ __forceinline__ void vit_embed_bwd_body(const bf16_t* __restrict__ dout, bf16_t* __restrict__ dpatches,
+                                                   float* __restrict__ part, int N, int T, int D, int per_g,
+                                                   const DropArgs* d) {
   const int64_t TD = (int64_t)T * D;
   const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
   if (r >= TD) return;
@@ -378,6 +405,14 @@ __global__ __launch_bounds__(256) void vit_embed_bwd_kernel(const bf16_t* __rest
       if (n + u >= n1) break;
       float f[8];
       unpack8(v[u], f);
+      if constexpr (DROP) {
+        float m[8];
+        drop_chunk(*d, drop_key(*d), (uint32_t)((n + u) * T + t), (uint32_t)(((n + u) * TD + r) >> 3), m);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) f[q] *= m[q];
+        v[u] = pack8(f);
+        unpack8(v[u], f);
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q) s[q] += f[q];
       if (t > 0) *(uint4*)(dpatches + (n + u) * (TD - D) + (r - D)) = v[u];
@@ -386,6 +421,19 @@ __global__ __launch_bounds__(256) void vit_embed_bwd_kernel(const bf16_t* __rest
   float* o = part + (size_t)blockIdx.y * TD + r;
   *(float4*)o = make_float4(s[0], s[1], s[2], s[3]);
   *(float4*)(o + 4) = make_float4(s[4], s[5], s[6], s[7]);
+}
+
+__global__ __launch_bounds__(256) void vit_embed_bwd_kernel(const bf16_t* __restrict__ dout,
+                                                            bf16_t* __restrict__ dpatches, float* __restrict__ part,
+                                                            int N, int T, int D, int per_g) {
+  vit_embed_bwd_body<false>(dout, dpatches, part, N, T, D, per_g, nullptr);
+}
+
+__global__ __launch_bounds__(256) void vit_embed_bwd_drop_kernel(const bf16_t* __restrict__ dout,
+                                                                 bf16_t* __restrict__ dpatches,
+                                                                 float* __restrict__ part, int N, int T, int D,
+                                                                 int per_g, DropArgs d) {
+  vit_embed_bwd_body<true>(dout, dpatches, part, N, T, D, per_g, &d);
 }
 
 // pass 2: dpos[r] += sum_g part[g][r]; dcls[c] += the same sum for token 0 (the class token's
@@ -626,6 +674,19 @@ MI_API int mi_vit_embed_fwd(const void* patches, const float* cls, const float* 
   return (int)hipGetLastError();
 }
 
+// mi_vit_embed_fwd with the embedding dropout folded in: out *= the element mask (thr, site) of the
+// [N * T][D] output, drawn from the device state block `state` (philox.h)
+MI_API int mi_vit_embed_fwd_drop(const void* patches, const float* cls, const float* pos, void* out, int N, int T,
+                                 int D, const void* state, int thr, int site, int rank, hipStream_t st) {
+  DropArgs d{};
+  if (D % 8 != 0 || N <= 0 || T < 2 || thr <= 0 || !drop_args(d, state, thr, site, 0, 0, rank, 1, (int64_t)N * T, D))
+    return (int)hipErrorInvalidValue;
+  const int64_t total8 = (int64_t)N * T * D / 8;
+  hipLaunchKernelGGL(vit_embed_fwd_drop_kernel, dim3((unsigned)cdiv(total8, 256)), dim3(256), 0, st,
+                     (const bf16_t*)patches, cls, pos, (bf16_t*)out, total8, T, D, d);
+  return (int)hipGetLastError();
+}
+
 // backward: dpatches [N][T-1][D] bf16 = dout[:, 1:], dpos [T][D] += sum_n dout[n], dcls [D] += sum_n
 // dout[n][0] (fp32, fixed-order sums; dpos / dcls may be null).  part: fp32 workspace of
 // mi_vit_embed_bwd_part_floats(N, T, D) floats.
@@ -642,6 +703,23 @@ MI_API int mi_vit_embed_bwd(const void* dout, void* dpatches, float* dpos, float
   const int64_t TD = (int64_t)T * D;
   hipLaunchKernelGGL(vit_embed_bwd_kernel, dim3((unsigned)cdiv(TD / 8, 256), G_used), dim3(256), 0, st,
                      (const bf16_t*)dout, (bf16_t*)dpatches, part, N, T, D, per_g);
+  if (dpos || dcls)
+    hipLaunchKernelGGL(vit_embed_bwd_sum_kernel, dim3((unsigned)cdiv(TD, 256)), dim3(256), 0, st, part, G_used,
+                       TD, D, dpos, dcls);
+  return (int)hipGetLastError();
+}
+
+// mi_vit_embed_bwd of mi_vit_embed_fwd_drop: the same with dout * mask (rounded to bf16) for dout
+MI_API int mi_vit_embed_bwd_drop(const void* dout, void* dpatches, float* dpos, float* dcls, float* part, int N, int T,
+                                 int D, const void* state, int thr, int site, int rank, hipStream_t st) {
+  DropArgs d{};
+  if (D % 8 != 0 || N <= 0 || T < 2 || thr <= 0 || !drop_args(d, state, thr, site, 0, 0, rank, 1, (int64_t)N * T, D))
+    return (int)hipErrorInvalidValue;
+  const int G = std::min(N, 16), per_g = cdiv(N, G);
+  const int G_used = cdiv(N, per_g);
+  const int64_t TD = (int64_t)T * D;
+  hipLaunchKernelGGL(vit_embed_bwd_drop_kernel, dim3((unsigned)cdiv(TD / 8, 256), G_used), dim3(256), 0, st,
+                     (const bf16_t*)dout, (bf16_t*)dpatches, part, N, T, D, per_g, d);
   if (dpos || dcls)
     hipLaunchKernelGGL(vit_embed_bwd_sum_kernel, dim3((unsigned)cdiv(TD, 256)), dim3(256), 0, st, part, G_used,
                        TD, D, dpos, dcls);

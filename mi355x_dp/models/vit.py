@@ -11,7 +11,10 @@ projection, attention output projection, both MLP projections and the head -- ru
 the MFMA kernels in bf16 with fp32 master weights in the flat DP engine.  On the GPU each
 encoder block is one fused autograd node (``mi355x_dp.ops.transformer.encoder_layer``):
 native LayerNorm kernels, GELU and residual adds in the GEMM epilogues, bias gradients as
-bf16 column sums.
+bf16 column sums.  Hidden ``dropout`` and ``stochastic_depth_prob`` (drop-path, row mode, torchvision's
+linear per-layer schedule) stay on that fused node: they are modes of its GEMM epilogues, with masks
+from the model's ``drop_state`` (``ops.transformer.DropState``; not part of ``state_dict()``).
+``attention_dropout > 0`` in training takes the per-op path.
 """
 from __future__ import annotations
 
@@ -87,9 +90,31 @@ class MLPBlock(nn.Sequential):
         return self[4](Fm.linear(h, self[3].weight, self[3].bias, out_bf16=True))
 
 
+def stochastic_depth_schedule(prob, num_layers):
+    """Per-layer drop-path probabilities: ``prob * l / (L - 1)`` (torchvision's linear rule), ``prob``
+    for a single layer."""
+    if num_layers <= 1:
+        return [float(prob)] * num_layers
+    return [float(prob) * l / (num_layers - 1) for l in range(num_layers)]
+
+
+def _check_prob(name, p):
+    if not 0.0 <= float(p) < 1.0:
+        raise ValueError(f"{name} must be in [0, 1), got {p}")
+    return float(p)
+
+
 class EncoderBlock(nn.Module):
-    def __init__(self, heads, dim, mlp_dim, dropout=0.0, attention_dropout=0.0):
+    def __init__(self, heads, dim, mlp_dim, dropout=0.0, attention_dropout=0.0, stochastic_depth_prob=0.0,
+                 layer_index=0):
         super().__init__()
+        _check_prob("dropout", dropout)
+        self.stochastic_depth_prob = _check_prob("stochastic_depth_prob", stochastic_depth_prob)
+        self.layer_index = int(layer_index)
+        # mask source of the fused path: the owning model's DropState (set by VisionTransformer; a
+        # block used on its own makes one at first need) and the block copy of the current forward
+        self.drop_state = None
+        self._drop_snap = None
         self.num_heads = heads
         self.ln_1 = LayerNorm(dim, eps=1e-6)
         self.self_attention = MultiheadSelfAttention(dim, heads, attention_dropout)
@@ -100,22 +125,48 @@ class EncoderBlock(nn.Module):
     def fused_params(self):
         return [self.get_parameter(n) for n in Tm.PARAM_ORDER]
 
+    def _layer_drop(self, device):
+        """This forward's LayerDrop (the model advanced the state and left the block copy; a block
+        on its own advances its own state)."""
+        if self.drop_state is None:
+            self.drop_state = Tm.DropState()
+        snap, self._drop_snap = self._drop_snap, None
+        if snap is None:
+            snap = self.drop_state.advance(device, snapshot=True)
+        return Tm.LayerDrop(self.drop_state, self.layer_index, self.dropout.p, self.stochastic_depth_prob, snap)
+
+    def _drop_path(self, h):
+        """row-mode stochastic depth of the per-op / CPU path, torch's RNG: a sample's branch is
+        dropped with probability p, the kept ones scaled by 1 / (1 - p)"""
+        p = self.stochastic_depth_prob
+        if p == 0.0 or not self.training:
+            return h
+        keep = torch.rand((h.shape[0],) + (1,) * (h.dim() - 1), device=h.device) >= p
+        return h * keep.to(h.dtype) / (1.0 - p)
+
     def forward(self, x):
-        fusable = (self.self_attention.dropout == 0.0 and self.dropout.p == 0.0 and self.mlp[2].p == 0.0) \
-            or not self.training
+        fusable = self.self_attention.dropout == 0.0 or not self.training
         if x.is_cuda and fusable and self.ln_1.weight.dtype == torch.float32:
-            return Tm.encoder_layer(x, self.num_heads, self.ln_1.eps, self.fused_params())
-        y = self.dropout(self.self_attention(self.ln_1(x))) + x
-        return self.mlp(self.ln_2(y)) + y
+            drop = None
+            if self.training and (self.dropout.p > 0.0 or self.stochastic_depth_prob > 0.0):
+                drop = self._layer_drop(x.device)
+            return Tm.encoder_layer(x, self.num_heads, self.ln_1.eps, self.fused_params(), drop=drop)
+        self._drop_snap = None
+        y = self._drop_path(self.dropout(self.self_attention(self.ln_1(x)))) + x
+        return self._drop_path(self.mlp(self.ln_2(y))) + y
 
 
 class Encoder(nn.Module):
-    def __init__(self, seq_length, num_layers, heads, dim, mlp_dim, dropout=0.0, attention_dropout=0.0):
+    def __init__(self, seq_length, num_layers, heads, dim, mlp_dim, dropout=0.0, attention_dropout=0.0,
+                 stochastic_depth_prob=0.0):
         super().__init__()
+        _check_prob("dropout", dropout)
+        _check_prob("stochastic_depth_prob", stochastic_depth_prob)
         self.pos_embedding = nn.Parameter(torch.empty(1, seq_length, dim).normal_(std=0.02))
         self.dropout = nn.Dropout(dropout)
+        sd = stochastic_depth_schedule(stochastic_depth_prob, num_layers)
         self.layers = nn.Sequential(OrderedDict(
-            (f"encoder_layer_{i}", EncoderBlock(heads, dim, mlp_dim, dropout, attention_dropout))
+            (f"encoder_layer_{i}", EncoderBlock(heads, dim, mlp_dim, dropout, attention_dropout, sd[i], i))
             for i in range(num_layers)))
         self.ln = LayerNorm(dim, eps=1e-6)
 
@@ -126,14 +177,21 @@ class Encoder(nn.Module):
 
 class VisionTransformer(nn.Module):
     def __init__(self, image_size=224, patch_size=16, num_layers=12, num_heads=12, hidden_dim=768, mlp_dim=3072,
-                 dropout=0.0, attention_dropout=0.0, num_classes=1000):
+                 dropout=0.0, attention_dropout=0.0, num_classes=1000, stochastic_depth_prob=0.0):
         super().__init__()
         self.image_size, self.patch_size, self.hidden_dim = image_size, patch_size, hidden_dim
         self.num_classes = num_classes
         self.conv_proj = Conv2d(3, hidden_dim, kernel_size=patch_size, stride=patch_size)
         seq = (image_size // patch_size) ** 2 + 1
         self.class_token = nn.Parameter(torch.zeros(1, 1, hidden_dim))
-        self.encoder = Encoder(seq, num_layers, num_heads, hidden_dim, mlp_dim, dropout, attention_dropout)
+        self.encoder = Encoder(seq, num_layers, num_heads, hidden_dim, mlp_dim, dropout, attention_dropout,
+                               stochastic_depth_prob)
+        # one mask state for the whole model (seed, rank, step), advanced once per training forward;
+        # a plain object, so state_dict() keeps the reference layout
+        self.drop_state = Tm.DropState()
+        self._drops = dropout > 0.0 or stochastic_depth_prob > 0.0
+        for blk in self.encoder.layers:
+            blk.drop_state = self.drop_state
         self.seq_length = seq
         self.heads = nn.Sequential(OrderedDict(head=Linear(hidden_dim, num_classes)))
         fan_in = 3 * patch_size * patch_size
@@ -151,6 +209,11 @@ class VisionTransformer(nn.Module):
         return x
 
     def forward(self, x):
+        snap = None
+        if self._drops and self.training and x.is_cuda:
+            snap = self.drop_state.advance(x.device, snapshot=True)
+            for blk in self.encoder.layers:
+                blk._drop_snap = snap
         if x.is_cuda:
             if x.shape[1] < 8:
                 x = Fm.pad_channels8(x)
@@ -164,7 +227,13 @@ class VisionTransformer(nn.Module):
             # head reads only the class token and LayerNorm is per token, so the final LayerNorm
             # runs on those rows alone -- the same output as encoder(x)[:, 0]
             enc = self.encoder
-            x = enc.layers(enc.dropout(Tm.vit_embed(x, self.class_token, enc.pos_embedding)))
+            if snap is not None and enc.dropout.p > 0.0:
+                # the embedding dropout rides on the embedding pass (mask site: layer = num_layers)
+                x = Tm.vit_embed(x, self.class_token, enc.pos_embedding,
+                                 drop=(self.drop_state, snap, len(enc.layers), enc.dropout.p))
+            else:
+                x = enc.dropout(Tm.vit_embed(x, self.class_token, enc.pos_embedding))
+            x = enc.layers(x)
             return self.heads(enc.ln(x[:, 0]))
         x = torch.cat([self.class_token.expand(n, -1, -1).to(x.dtype), x], dim=1)
         x = self.encoder(x)

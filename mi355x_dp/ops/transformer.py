@@ -20,6 +20,13 @@ extra MFMA against a ones operand on fragments it already holds -- no second pas
 The data-gradient GEMMs read the flat engine's cached transposed weights.  Weight gradients go
 straight into the flat fp32 gradient buffer of the DP engine (``functional._grad_buffer``).
 
+Regularisation inside the layer (``encoder_layer(..., drop=LayerDrop(...))``): hidden dropout and
+stochastic depth (drop-path, row mode) are modes of the same epilogues -- ``y = x + m * (o Woᵀ + b)``
+with ``m`` = element mask x per-sample mask, ``g = m * gelu(.)`` with ``gelu'`` stored already masked --
+drawn by a counter-based generator (Philox4x32-10, ``csrc/kernels/philox.h``) from
+(seed, rank, step, site, position), so the backward recomputes them (``mi_drop_bwd``) and no mask is
+saved.  ``DropState`` owns seed and step on the device.
+
 Reference: the ViT-B/16 config is a BASELINE.json target (config 5), not part of the
 reference repo; semantics follow torchvision ``vision_transformer.EncoderBlock``.
 """
@@ -109,6 +116,183 @@ def _dgrad(dy2, weight, epi=EPI_NONE, aux=None):
     if epi == EPI_NONE and BLAS_DGRAD:
         return torch.matmul(dy2, weight_bf16(weight))
     return _gemm(dy2, linear_weight_t(weight), None, epi, aux)
+
+
+# ------------------------------------------------------------------ dropout / stochastic depth
+# mask sites of layer l: 8 l + kind (the embedding dropout: layer = num_layers, kind 0)
+SITE_ATTN_DROP, SITE_GELU_DROP, SITE_MLP_DROP, SITE_ATTN_PATH, SITE_MLP_PATH = range(5)
+DROP_RESIDUAL, DROP_GELU = 1, 2  # kinds of the dropped GEMM epilogues
+
+
+def drop_threshold(p) -> int:
+    """``thr = round(p * 65536)`` of the keep rule ``r >= thr`` on 16-bit draws; 0: the site is
+    inactive.  ``ValueError`` outside ``0 <= p < 1``."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"drop probability must be in [0, 1), got {p}")
+    return min(int(p * 65536.0 + 0.5), 65535)
+
+
+def _default_rank() -> int:
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+class DropState:
+    """Seed and step of the dropout / stochastic-depth masks.  On the GPU they live in a device
+    block of two 64-bit words that the kernels read through a pointer and a one-thread native kernel
+    advances, so a captured graph draws new masks on every replay.  ``rank`` (default: the process
+    group's, resolved at first use; 0 without one) goes into the counter, so ranks draw different
+    masks from one seed.  Not a module: it never appears in a model's ``state_dict()``;
+    ``utils.checkpoint`` stores ``state_dict()`` beside it."""
+
+    def __init__(self, seed=0, rank=None):
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._rank = None if rank is None else self._check_rank(rank)
+        self._step = 0
+        self._block = None
+
+    @staticmethod
+    def _check_rank(rank):
+        rank = int(rank)
+        if not 0 <= rank < 65536:
+            raise ValueError(f"rank must be in [0, 65536), got {rank}")
+        return rank
+
+    @property
+    def seed(self) -> int:
+        return self._seed
+
+    @property
+    def rank(self) -> int:
+        if self._rank is None:
+            self._rank = self._check_rank(_default_rank())
+        return self._rank
+
+    @property
+    def step(self) -> int:
+        if self._block is not None:
+            self._step = int(self._block[1].item())
+        return self._step
+
+    @step.setter
+    def step(self, value):
+        self._step = int(value)
+        if self._block is not None:
+            self._block[1] = self._step
+
+    def reseed(self, seed, rank=None):
+        """New seed (and rank); the step restarts at 0."""
+        self._seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if rank is not None:
+            self._rank = self._check_rank(rank)
+        self._step = 0
+        self._block = None
+
+    def block(self, device):
+        """The live device block ``[seed, step]`` (int64) on ``device``."""
+        device = torch.device(device)
+        if self._block is None or self._block.device != device:
+            step = self.step
+            s = self._seed - (1 << 64) if self._seed >= (1 << 63) else self._seed
+            self._block = torch.tensor([s, step], dtype=torch.int64, device=device)
+        return self._block
+
+    def _advance(self, device, inc, snapshot):
+        blk = self.block(device)
+        snap = torch.empty(2, dtype=torch.int64, device=blk.device) if snapshot else None
+        _lib.call("mi_drop_state_advance", ptr(blk), ptr(snap), inc, stream_of(blk))
+        return snap
+
+    def advance(self, device=None, snapshot=False):
+        """step += 1 (on the device when the block lives there).  ``snapshot=True`` returns a copy of
+        the advanced block: what the kernels of one forward / backward pair read, whatever advances
+        later."""
+        if device is None and self._block is not None:
+            device = self._block.device
+        if device is None or torch.device(device).type != "cuda":  # host only: nothing on a device reads it
+            self._step = self.step + 1
+            return None
+        return self._advance(device, 1, snapshot)
+
+    def snapshot(self, device):
+        """A copy of the current block, without advancing."""
+        return self._advance(device, 0, True)
+
+    def state_dict(self):
+        return {"seed": self._seed, "rank": self.rank, "step": self.step}
+
+    def load_state_dict(self, sd):
+        """Restores seed and step.  The rank stays this process's own (a checkpoint is written by
+        rank 0 and read by every rank)."""
+        self._seed = int(sd["seed"]) & 0xFFFFFFFFFFFFFFFF
+        self._step = int(sd["step"])
+        self._block = None
+
+
+class LayerDrop:
+    """Regularisation of one fused encoder layer: ``dropout`` (hidden dropout after out_proj, GELU
+    and fc2) and ``stochastic_depth`` (row mode, both residual branches) of layer ``layer``, masks
+    drawn from ``state`` (a ``DropState``).  ``snap``: the block copy of this forward
+    (``DropState.advance(snapshot=True)``), shared by the layers of one model forward; without it
+    the layer takes its own copy of the current block."""
+    __slots__ = ("state", "layer", "dropout", "stochastic_depth", "snap")
+
+    def __init__(self, state, layer, dropout=0.0, stochastic_depth=0.0, snap=None):
+        self.state, self.layer, self.snap = state, int(layer), snap
+        self.dropout, self.stochastic_depth = float(dropout), float(stochastic_depth)
+
+
+class _Drop:
+    """A LayerDrop resolved for one call: thresholds, site base, rank and the block copy."""
+    __slots__ = ("snap", "rank", "base", "thr_e", "thr_r")
+
+    def site(self, kind):
+        return self.base + kind
+
+
+def _resolve_drop(drop, device):
+    if drop is None:
+        return None
+    thr_e, thr_r = drop_threshold(drop.dropout), drop_threshold(drop.stochastic_depth)
+    if thr_e == 0 and thr_r == 0:
+        return None
+    if not 0 <= 8 * drop.layer + 7 < 65536:
+        raise ValueError(f"layer index {drop.layer} is outside the mask site range")
+    d = _Drop()
+    d.snap = drop.snap if drop.snap is not None else drop.state.snapshot(device)
+    d.rank, d.base, d.thr_e, d.thr_r = drop.state.rank, 8 * drop.layer, thr_e, thr_r
+    return d
+
+
+def _gemm_drop(a2, w16, bias, kind, aux, d, site_e, thr_e, site_r=0, thr_r=0, rows_per_sample=1):
+    """``_gemm`` with a dropped epilogue: DROP_RESIDUAL out = (a2 w16ᵀ + bias) * m + aux, DROP_GELU
+    out = gelu(.) * m and gelu'(.) * m; m = element mask (thr_e, site_e) x per-sample mask (thr_r, site_r)."""
+    M, K = a2.shape
+    N = w16.shape[0]
+    out = torch.empty((M, N), dtype=BF16, device=a2.device)
+    if kind == DROP_GELU:
+        aux = torch.empty((M, N), dtype=BF16, device=a2.device)
+    _lib.call("mi_gemm_nt_epi_drop", ptr(a2), ptr(w16), ptr(out), ptr(bias), ptr(aux), kind, M, N, K, K, K, N,
+              ptr(d.snap), thr_e, site_e, thr_r, site_r, d.rank, rows_per_sample, stream_of(a2))
+    return (out, aux) if kind == DROP_GELU else out
+
+
+def _drop_bwd(dz2, d, site_e, thr_e, site_r, thr_r, rows_per_sample):
+    """bf16(dz * m): the gradient a dropped residual branch hands to its GEMMs (the masks recomputed)."""
+    M, N = dz2.shape
+    out = torch.empty_like(dz2)
+    _lib.call("mi_drop_bwd", ptr(dz2), ptr(out), M, N, ptr(d.snap), thr_e, site_e, thr_r, site_r, d.rank,
+              rows_per_sample, stream_of(dz2))
+    return out
+
+
+def drop_mask(M, N, state_block, rank, site_e=0, thr_e=0, site_r=0, thr_r=0, rows_per_sample=1):
+    """fp32 [M][N] multiplier matrix of a site, from the kernels' own device function (tests, debugging)."""
+    out = torch.empty((M, N), dtype=F32, device=state_block.device)
+    _lib.call("mi_drop_mask", ptr(out), M, N, ptr(state_block), thr_e, site_e, thr_r, site_r, rank, rows_per_sample,
+              stream_of(out))
+    return out
 
 
 # ------------------------------------------------------------------ attention
@@ -221,30 +405,43 @@ PARAM_ORDER = ("ln_1.weight", "ln_1.bias", "self_attention.in_proj_weight", "sel
                "mlp.0.weight", "mlp.0.bias", "mlp.3.weight", "mlp.3.bias")
 
 
-def _layer_forward(x2, B, T, heads, eps, params, need_grad):
+def _layer_forward(x2, B, T, heads, eps, params, need_grad, d=None):
     ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, w1, b1, w2, b2 = params
     h1, m1, r1 = _ln_fwd(x2, ln1w, ln1b, eps)
     qkv = _gemm(h1, weight_bf16(wqkv), bqkv)
     o, attn = _attn_fwd(qkv, B, T, heads, need_grad)
-    y = _gemm(o, weight_bf16(wo), bo, EPI_RESIDUAL, x2)
+    if d is None:
+        y = _gemm(o, weight_bf16(wo), bo, EPI_RESIDUAL, x2)
+    else:
+        y = _gemm_drop(o, weight_bf16(wo), bo, DROP_RESIDUAL, x2, d, d.site(SITE_ATTN_DROP), d.thr_e,
+                       d.site(SITE_ATTN_PATH), d.thr_r, T)
     h2, m2, r2 = _ln_fwd(y, ln2w, ln2b, eps)
-    g, u = _gemm(h2, weight_bf16(w1), b1, EPI_GELU)  # u = gelu'(pre-activation): all the backward needs
-    z = _gemm(g, weight_bf16(w2), b2, EPI_RESIDUAL, y)
+    # u = gelu'(pre-activation) (x the dropout mask): all the backward needs
+    if d is None or d.thr_e == 0:
+        g, u = _gemm(h2, weight_bf16(w1), b1, EPI_GELU)
+    else:
+        g, u = _gemm_drop(h2, weight_bf16(w1), b1, DROP_GELU, None, d, d.site(SITE_GELU_DROP), d.thr_e)
+    if d is None:
+        z = _gemm(g, weight_bf16(w2), b2, EPI_RESIDUAL, y)
+    else:
+        z = _gemm_drop(g, weight_bf16(w2), b2, DROP_RESIDUAL, y, d, d.site(SITE_MLP_DROP), d.thr_e,
+                       d.site(SITE_MLP_PATH), d.thr_r, T)
     saved = (x2, h1, m1, r1, qkv, o, y, h2, m2, r2, u, g) if need_grad else None
     return z, saved, attn
 
 
 class _EncoderLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, heads, eps, *params):
+    def forward(ctx, x, heads, eps, d, *params):
         B, T, D = x.shape
         x2 = x.reshape(B * T, D)
         if x2.dtype != BF16:
             x2 = x2.to(BF16)
         x2 = x2.contiguous()
-        z, saved, attn = _layer_forward(x2, B, T, heads, eps, params, True)
+        z, saved, attn = _layer_forward(x2, B, T, heads, eps, params, True, d)
         ctx.save_for_backward(*saved, *params)
         ctx.attn = attn
+        ctx.drop = d  # thresholds, sites and this forward's block copy: the backward redraws the masks
         ctx.dims = (B, T, D, heads)
         ctx.in_dtype = x.dtype
         return z.view(B, T, D)
@@ -258,15 +455,21 @@ class _EncoderLayer(torch.autograd.Function):
         if dz2.dtype != BF16:
             dz2 = dz2.to(BF16)
         dz2 = dz2.contiguous()
-        # MLP
-        d_w2, d_b2 = _wbgrad(w2, b2, dz2, g)
-        du = _dgrad(dz2, w2, EPI_GELU_BWD, u)
+        d = ctx.drop
+        ctx.drop = None
+        # MLP (a dropped branch's GEMMs see the masked gradient; the residual path keeps dz)
+        dzm = dz2 if d is None else _drop_bwd(dz2, d, d.site(SITE_MLP_DROP), d.thr_e, d.site(SITE_MLP_PATH),
+                                              d.thr_r, T)
+        d_w2, d_b2 = _wbgrad(w2, b2, dzm, g)
+        du = _dgrad(dzm, w2, EPI_GELU_BWD, u)
         d_w1, d_b1 = _wbgrad(w1, b1, du, h2)
         dh2 = _dgrad(du, w1)
         dy, d_ln2w, d_ln2b = _ln_bwd(dh2, y, ln2w, ln2b, m2, r2, dres=dz2)
         # attention
-        d_wo, d_bo = _wbgrad(wo, bo, dy, o)
-        do = _dgrad(dy, wo)
+        dym = dy if d is None else _drop_bwd(dy, d, d.site(SITE_ATTN_DROP), d.thr_e, d.site(SITE_ATTN_PATH),
+                                             d.thr_r, T)
+        d_wo, d_bo = _wbgrad(wo, bo, dym, o)
+        do = _dgrad(dym, wo)
         dqkv = _attn_bwd(ctx.attn, qkv, do, B, T, heads)
         ctx.attn = None
         d_wqkv, d_bqkv = _wbgrad(wqkv, bqkv, dqkv, h1)
@@ -275,17 +478,20 @@ class _EncoderLayer(torch.autograd.Function):
         dx = dx.view(B, T, D)
         if ctx.in_dtype != BF16:
             dx = dx.to(ctx.in_dtype)
-        return (dx, None, None, d_ln1w, d_ln1b, d_wqkv, d_bqkv, d_wo, d_bo, d_ln2w, d_ln2b, d_w1, d_b1, d_w2,
+        return (dx, None, None, None, d_ln1w, d_ln1b, d_wqkv, d_bqkv, d_wo, d_bo, d_ln2w, d_ln2b, d_w1, d_b1, d_w2,
                 d_b2)
 
 
-def encoder_layer(x, heads, eps, params):
-    """x [B, T, D] (cuda) -> [B, T, D] bf16.  ``params`` in ``PARAM_ORDER``."""
+def encoder_layer(x, heads, eps, params, drop=None):
+    """x [B, T, D] (cuda) -> [B, T, D] bf16.  ``params`` in ``PARAM_ORDER``.  ``drop``: a ``LayerDrop``
+    (hidden dropout / stochastic depth of a training forward); ``None`` or all probabilities 0: the
+    launches are those of the plain layer."""
+    d = _resolve_drop(drop, x.device)
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
-        return _EncoderLayer.apply(x, heads, eps, *params)
+        return _EncoderLayer.apply(x, heads, eps, d, *params)
     B, T, D = x.shape
     x2 = x.reshape(B * T, D).to(BF16).contiguous()
-    z, _, _ = _layer_forward(x2, B, T, heads, eps, params, False)
+    z, _, _ = _layer_forward(x2, B, T, heads, eps, params, False, d)
     return z.view(B, T, D)
 
 
@@ -382,15 +588,22 @@ class _VitEmbed(torch.autograd.Function):
     """[class token ; patch embeddings] + position embedding as one native pass
     (``mi_vit_embed_fwd``); backward: the patches' dense gradient plus the fixed-order batch sums
     for the position embedding and the class token (``mi_vit_embed_bwd``) -- no concatenation,
-    broadcast-add, cast or reduction launches."""
+    broadcast-add, cast or reduction launches.  ``drop`` = (block copy, rank, site, threshold): the
+    embedding dropout folded into both passes (the backward redraws the mask)."""
 
     @staticmethod
-    def forward(ctx, patches, cls, pos):
+    def forward(ctx, patches, cls, pos, drop=None):
         N, P, D = patches.shape
         T = P + 1
         p = patches.contiguous()
         out = torch.empty((N, T, D), dtype=BF16, device=p.device)
-        _lib.call("mi_vit_embed_fwd", ptr(p), ptr(cls), ptr(pos), ptr(out), N, T, D, stream_of(p))
+        if drop is None:
+            _lib.call("mi_vit_embed_fwd", ptr(p), ptr(cls), ptr(pos), ptr(out), N, T, D, stream_of(p))
+        else:
+            snap, rank, site, thr = drop
+            _lib.call("mi_vit_embed_fwd_drop", ptr(p), ptr(cls), ptr(pos), ptr(out), N, T, D, ptr(snap), thr, site,
+                      rank, stream_of(p))
+        ctx.drop = drop
         ctx.params = (cls, pos)
         ctx.shape = (N, T, D)
         return out
@@ -404,15 +617,27 @@ class _VitEmbed(torch.autograd.Function):
         gpos = _grad_buffer(pos) if ctx.needs_input_grad[2] else None
         gcls = _grad_buffer(cls) if ctx.needs_input_grad[1] else None
         part = torch.empty(int(_lib.load().mi_vit_embed_bwd_part_floats(N, T, D)), dtype=F32, device=d.device)
-        _lib.call("mi_vit_embed_bwd", ptr(d), ptr(dp), ptr(gpos), ptr(gcls), ptr(part), N, T, D, stream_of(d))
+        if ctx.drop is None:
+            _lib.call("mi_vit_embed_bwd", ptr(d), ptr(dp), ptr(gpos), ptr(gcls), ptr(part), N, T, D, stream_of(d))
+        else:
+            snap, rank, site, thr = ctx.drop
+            _lib.call("mi_vit_embed_bwd_drop", ptr(d), ptr(dp), ptr(gpos), ptr(gcls), ptr(part), N, T, D, ptr(snap),
+                      thr, site, rank, stream_of(d))
         dcls = _finish_grad(cls, gcls) if gcls is not None else None
         dpos = _finish_grad(pos, gpos) if gpos is not None else None
-        return dp, dcls, dpos
+        return dp, dcls, dpos, None
 
 
-def vit_embed(patches, cls, pos):
-    """bf16 [N][T][D] tokens = cat(cls, patches) + pos for fp32 ``cls`` [1,1,D] / ``pos`` [1,T,D]."""
-    return _VitEmbed.apply(patches, cls, pos)
+def vit_embed(patches, cls, pos, drop=None):
+    """bf16 [N][T][D] tokens = cat(cls, patches) + pos for fp32 ``cls`` [1,1,D] / ``pos`` [1,T,D].
+    ``drop`` = (state, snap, layer, p): the embedding dropout (site 8 * layer, element mask) of a
+    training forward, folded into the pass."""
+    if drop is not None:
+        state, snap, layer, p = drop
+        thr = drop_threshold(p)
+        drop = None if thr == 0 else (snap if snap is not None else state.snapshot(patches.device), state.rank,
+                                      8 * layer + SITE_ATTN_DROP, thr)
+    return _VitEmbed.apply(patches, cls, pos, drop)
 
 
 def layer_norm(x, weight, bias, eps):

@@ -5,7 +5,8 @@
   contiguous tensors; a DDP/DataParallel wrapper keeps its ``module.`` prefix exactly as
   in cifar10-distributed-smddp-gpu.py:205-208).
 * ``save_checkpoint`` / ``load_checkpoint`` -- resumable training state the reference
-  lacks: model + optimizer (flat momentum buffer) + step/epoch + RNG states, written
+  lacks: model + optimizer (flat momentum buffer) + step/epoch + RNG states (and the model's
+  dropout / stochastic-depth ``drop_state`` when it has one), written
   atomically by rank 0 to a separate file (never changes model.pth), restored on every
   rank (map_location to the local device) with ``weights_only=True``.  An optimizer whose state is
   sharded over ranks (``FlatSGD`` under ``DataParallel(shard_optimizer=True)``: each rank holds the
@@ -55,6 +56,16 @@ def optim_shard_path(path: str, rank: int, world: int) -> str:
     return f"{path}.optim-rank{rank}-of-{world}"
 
 
+def _drop_state(model):
+    """the model's dropout / stochastic-depth state (ops.transformer.DropState: seed, rank, step) --
+    not a module, so not part of ``state_dict()``; looked up through a DDP-style ``.module`` wrapper"""
+    for m in (model, getattr(model, "module", None)):
+        ds = getattr(m, "drop_state", None) if m is not None else None
+        if ds is not None:
+            return ds
+    return None
+
+
 def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, step: int = 0, epoch: int = 0,
                     extra: Optional[Dict[str, Any]] = None) -> Optional[str]:
     osd = optimizer.state_dict() if optimizer is not None else None
@@ -76,6 +87,9 @@ def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, step: int
         state["rng_cuda"] = torch.cuda.get_rng_state()
     if optimizer is not None:
         state["optimizer"] = {"sharded_over": _world()} if sharded else osd
+    ds = _drop_state(model)
+    if ds is not None:
+        state["drop_state"] = ds.state_dict()
     if extra:
         state["extra"] = extra
     os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
@@ -97,6 +111,9 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, map_locat
             osd = torch.load(optim_shard_path(path, _rank(), _world()), map_location=map_location or "cpu",
                              weights_only=True)
         optimizer.load_state_dict(osd)
+    ds = _drop_state(model)
+    if ds is not None and "drop_state" in state:
+        ds.load_state_dict(state["drop_state"])
     if "rng_cpu" in state:
         torch.set_rng_state(state["rng_cpu"])
     if "rng_cuda" in state and torch.cuda.is_available():
