@@ -25,13 +25,59 @@ inline int ew_grid(int64_t n) {
   return (int)(g < 1 ? 1 : (g < 8192 ? g : 8192));
 }
 
+// Sum of s over the block, valid in thread 0: a xor tree over the 64 lanes of every wave, then
+// thread 0 adds the wave partials in index order.
+template <int N>
+__device__ __forceinline__ double block_sum(double s) {
+  __shared__ double red[N / 64];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = red[0];
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < N / 64; ++w) t += red[w];
+  }
+  return t;
+}
+
+// VEC: 16-byte accesses (bf16: 8-byte); otherwise the same four elements one by one
+template <bool VEC>
+__device__ __forceinline__ float4 ld4(const float* __restrict__ p, int64_t i) {
+  if (VEC) return ((const float4*)p)[i];
+  const float* q = p + (i << 2);
+  return make_float4(q[0], q[1], q[2], q[3]);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void st4(float* __restrict__ p, int64_t i, const float4& v) {
+  if (VEC) {
+    ((float4*)p)[i] = v;
+  } else {
+    float* q = p + (i << 2);
+    q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
+  }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void st4bf(bf16_t* __restrict__ p16, int64_t i, const float4& v) {
+  if (VEC) {
+    uint2 o;
+    o.x = pack2bf(v.x, v.y);
+    o.y = pack2bf(v.z, v.w);
+    ((uint2*)p16)[i] = o;
+  } else {
+    bf16_t* q = p16 + (i << 2);
+    q[0] = f2bf(v.x), q[1] = f2bf(v.y), q[2] = f2bf(v.z), q[3] = f2bf(v.w);
+  }
+}
+
 // -------------------------------------------------------------------- squared gradient norm
 // Block b writes its fp64 partial to part[b]; sqnorm_final_kernel sums all slots of all segments
 // in a fixed order.  16-byte loads over the aligned body, scalar loads for an unaligned head
 // (x only 4-byte aligned) and the tail.
 __global__ __launch_bounds__(NT) void sqnorm_partial_kernel(const float* __restrict__ x, int64_t n,
                                                             double* __restrict__ part) {
-  __shared__ double red[NT / 64];
   const int64_t tid = blockIdx.x * (int64_t)NT + threadIdx.x, nthr = (int64_t)gridDim.x * NT;
   int64_t head = (int64_t)(((16 - ((uintptr_t)x & 15)) & 15) >> 2);
   if (head > n) head = n;
@@ -49,26 +95,31 @@ __global__ __launch_bounds__(NT) void sqnorm_partial_kernel(const float* __restr
   const int64_t tail0 = head + (nvec << 2);
   if (tid < head) s += (double)x[tid] * (double)x[tid];
   if (tid < n - tail0) s += (double)x[tail0 + tid] * (double)x[tail0 + tid];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+  s = block_sum<NT>(s);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(NT) void sqnorm_final_kernel(const double* __restrict__ part, int nparts,
                                                           double* __restrict__ out) {
-  __shared__ double red[NT / 64];
   double s = 0.0;
   for (int i = threadIdx.x; i < nparts; i += NT) s += part[i];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = red[0] + red[1] + red[2] + red[3];
+  s = block_sum<NT>(s);
+  if (threadIdx.x == 0) out[0] = s;
 }
 
 // ------------------------------------------------------------------------------------ prep
 // clip_grad_norm_ semantics: coef = min(1, max_norm / (total_norm + 1e-6)), a NaN norm gives a NaN
-// coefficient (torch clamps with max=1, which keeps NaN), an infinite norm gives 0.
+// coefficient (torch clamps with max=1, which keeps NaN), an infinite norm gives 0.  Both state
+// blocks keep total_norm in [2]; without clipping it is left alone and the coefficient is 1.
+__device__ __forceinline__ double clip_coef(double* __restrict__ st, const double* __restrict__ sumsq,
+                                            double max_norm, double grad_scale, int clip) {
+  if (!clip) return 1.0;
+  const double total = grad_scale * sqrt(sumsq[0]);
+  const double c = max_norm / (total + 1e-6);
+  st[2] = total;
+  return c > 1.0 ? 1.0 : c;
+}
+
 __global__ void adamw_prep_kernel(double* __restrict__ st, const double* __restrict__ sumsq, double beta1,
                                   double beta2, double wd, double max_norm, double grad_scale, int clip) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -76,13 +127,7 @@ __global__ void adamw_prep_kernel(double* __restrict__ st, const double* __restr
   const double lr = st[1];
   const double bc1 = 1.0 - pow(beta1, t);
   const double bc2 = 1.0 - pow(beta2, t);
-  double coef = 1.0;
-  if (clip) {
-    const double total = grad_scale * sqrt(sumsq[0]);
-    const double c = max_norm / (total + 1e-6);
-    coef = c > 1.0 ? 1.0 : c;
-    st[2] = total;
-  }
+  const double coef = clip_coef(st, sumsq, max_norm, grad_scale, clip);
   st[0] = t;
   st[3] = coef;
   st[4] = lr / bc1;
@@ -145,12 +190,7 @@ __global__ __launch_bounds__(NT) void adamw_flat_kernel(float* __restrict__ p, c
       ((float4*)p)[i] = pp;
       ((float4*)m)[i] = mm;
       ((float4*)v)[i] = vv;
-      if (p16) {
-        uint2 o;
-        o.x = pack2bf(pp.x, pp.y);
-        o.y = pack2bf(pp.z, pp.w);
-        ((uint2*)p16)[i] = o;
-      }
+      if (p16) st4bf<true>(p16, i, pp);
     }
   }
   for (int64_t i = (nvec << 2) + tid; i < n; i += nthr) {
@@ -184,36 +224,6 @@ __global__ __launch_bounds__(NT) void adamw_flat_kernel(float* __restrict__ p, c
 // LARS state block (doubles):  [0] step t  [1] lr
 // LAMB state block (doubles):  [0] step t  [1] lr  [2] total_norm  [3] clip coefficient
 //                              [4] bc1     [5] bc2 [6] grad_scale * coef          [7] unused
-template <bool VEC>
-__device__ __forceinline__ float4 ld4(const float* __restrict__ p, int64_t i) {
-  if (VEC) return ((const float4*)p)[i];
-  const float* q = p + (i << 2);
-  return make_float4(q[0], q[1], q[2], q[3]);
-}
-
-template <bool VEC>
-__device__ __forceinline__ void st4(float* __restrict__ p, int64_t i, const float4& v) {
-  if (VEC) {
-    ((float4*)p)[i] = v;
-  } else {
-    float* q = p + (i << 2);
-    q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void st4bf(bf16_t* __restrict__ p16, int64_t i, const float4& v) {
-  if (VEC) {
-    uint2 o;
-    o.x = pack2bf(v.x, v.y);
-    o.y = pack2bf(v.z, v.w);
-    ((uint2*)p16)[i] = o;
-  } else {
-    bf16_t* q = p16 + (i << 2);
-    q[0] = f2bf(v.x), q[1] = f2bf(v.y), q[2] = f2bf(v.z), q[3] = f2bf(v.w);
-  }
-}
-
 __device__ __forceinline__ double sq4(const float4& a) {
   double s = (double)a.x * (double)a.x;
   s += (double)a.y * (double)a.y;
@@ -253,21 +263,14 @@ constexpr int RT = 1024;
 __global__ __launch_bounds__(RT) void seg_reduce_kernel(const double* __restrict__ upart, int64_t set_stride,
                                                         const int64_t* __restrict__ table, int P,
                                                         double* __restrict__ out) {
-  __shared__ double red[RT / 64];
   const int p = blockIdx.x, set = blockIdx.y;
   const int64_t lo = table[2 * p], hi = table[2 * p + 1];
   const double* src = upart + set * set_stride;
   double s = 0.0;
 #pragma unroll 4
   for (int64_t u = lo + threadIdx.x; u < hi; u += RT) s += src[u];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < RT / 64; ++w) t += red[w];
-    out[(int64_t)set * P + p] = t;
-  }
+  s = block_sum<RT>(s);
+  if (threadIdx.x == 0) out[(int64_t)set * P + p] = s;
 }
 
 // ---------------------------------------------------------------------------- trust ratios
@@ -337,18 +340,11 @@ __global__ __launch_bounds__(NT) void lars_flat_kernel(float* __restrict__ p, co
 }
 
 // ------------------------------------------------------------------------------------ LAMB
-// clip coefficient as in adamw_prep_kernel (clip_grad_norm_ semantics)
 __global__ void lamb_prep_kernel(double* __restrict__ st, const double* __restrict__ sumsq, double beta1,
                                  double beta2, double max_norm, double grad_scale, int clip) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const double t = st[0] + 1.0;
-  double coef = 1.0;
-  if (clip) {
-    const double total = grad_scale * sqrt(sumsq[0]);
-    const double c = max_norm / (total + 1e-6);
-    coef = c > 1.0 ? 1.0 : c;
-    st[2] = total;
-  }
+  const double coef = clip_coef(st, sumsq, max_norm, grad_scale, clip);
   st[0] = t;
   st[3] = coef;
   st[4] = 1.0 - pow(beta1, t);
@@ -446,8 +442,24 @@ __global__ __launch_bounds__(NT) void lamb_apply_kernel(float* __restrict__ p, c
   }
 }
 
+// a launch takes the VEC path when its fp32 arrays are 16-byte aligned and its bf16 copy (or null) 8-byte
 inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+
+inline bool aligned8(const void* p16) { return ((uintptr_t)p16 & 7) == 0; }
+
+// kernel<true> when vec, else kernel<false>: NT threads, `blocks` blocks, on stream st
+#define LAUNCH_VEC(kernel, vec, blocks, st, ...)                                           \
+  do {                                                                                     \
+    if (vec)                                                                               \
+      hipLaunchKernelGGL(kernel<true>, dim3(blocks), dim3(NT), 0, st, __VA_ARGS__);        \
+    else                                                                                   \
+      hipLaunchKernelGGL(kernel<false>, dim3(blocks), dim3(NT), 0, st, __VA_ARGS__);       \
+  } while (0)
+
+inline LambConsts lamb_consts(double beta1, double beta2, double eps, double wd) {
+  return {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, (float)wd};
 }
 
 }  // namespace
@@ -488,14 +500,9 @@ MI_API int mi_adamw_flat(float* p, const float* g, float* m, float* v, void* p16
   if (n < 0) return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
   const AdamConsts c = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps};
-  const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
-                   ((uintptr_t)p16 & 7) == 0;
-  if (vec)
-    hipLaunchKernelGGL(adamw_flat_kernel<true>, dim3(ew_grid((n + 3) / 4)), dim3(NT), 0, st, p, g, m, v,
-                       (bf16_t*)p16, n, state, dmap, unit_base, c);
-  else
-    hipLaunchKernelGGL(adamw_flat_kernel<false>, dim3(ew_grid(n)), dim3(NT), 0, st, p, g, m, v, (bf16_t*)p16, n,
-                       state, dmap, unit_base, c);
+  const bool vec = aligned16(p, g, m, v) && aligned8(p16);
+  LAUNCH_VEC(adamw_flat_kernel, vec, ew_grid(vec ? (n + 3) / 4 : n), st, p, g, m, v, (bf16_t*)p16, n, state, dmap,
+             unit_base, c);
   return (int)hipGetLastError();
 }
 
@@ -507,10 +514,7 @@ MI_API int mi_seg_sqnorm_units(const float* a, const float* b, int64_t n, double
   if (n < 0 || (n & 63) || (b && !pb)) return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
   const int64_t nvec = n >> 2;
-  if (aligned16(a, b))
-    hipLaunchKernelGGL(seg_unit_sq_kernel<true>, dim3(ew_grid(nvec)), dim3(NT), 0, st, a, b, nvec, pa, pb);
-  else
-    hipLaunchKernelGGL(seg_unit_sq_kernel<false>, dim3(ew_grid(nvec)), dim3(NT), 0, st, a, b, nvec, pa, pb);
+  LAUNCH_VEC(seg_unit_sq_kernel, aligned16(a, b), ew_grid(nvec), st, a, b, nvec, pa, pb);
   return (int)hipGetLastError();
 }
 
@@ -548,12 +552,8 @@ MI_API int mi_lars_flat(float* p, const float* g, float* buf, void* p16, int64_t
   if (n == 0) return 0;
   const LarsConsts c = {(float)momentum, (float)wd, (float)grad_scale};
   const int64_t nvec = n >> 2;
-  if (aligned16(p, g, buf) && ((uintptr_t)p16 & 7) == 0)
-    hipLaunchKernelGGL(lars_flat_kernel<true>, dim3(ew_grid(nvec)), dim3(NT), 0, st, p, g, buf, (bf16_t*)p16, nvec,
-                       state, pidx, excl, q, unit_base, c);
-  else
-    hipLaunchKernelGGL(lars_flat_kernel<false>, dim3(ew_grid(nvec)), dim3(NT), 0, st, p, g, buf, (bf16_t*)p16, nvec,
-                       state, pidx, excl, q, unit_base, c);
+  LAUNCH_VEC(lars_flat_kernel, aligned16(p, g, buf) && aligned8(p16), ew_grid(nvec), st, p, g, buf, (bf16_t*)p16,
+             nvec, state, pidx, excl, q, unit_base, c);
   return (int)hipGetLastError();
 }
 
@@ -572,15 +572,9 @@ MI_API int mi_lamb_moments(const float* p, const float* g, float* m, float* v, i
                            double beta1, double beta2, double eps, double wd, hipStream_t st) {
   if (n < 0 || (n & 63)) return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
-  const LambConsts c = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                        (float)wd};
   const int64_t nvec = n >> 2;
-  if (aligned16(p, g, m, v))
-    hipLaunchKernelGGL(lamb_moments_kernel<true>, dim3(ew_grid(nvec)), dim3(NT), 0, st, p, g, m, v, nvec, state,
-                       pidx, excl, unit_base, pw, pu, c);
-  else
-    hipLaunchKernelGGL(lamb_moments_kernel<false>, dim3(ew_grid(nvec)), dim3(NT), 0, st, p, g, m, v, nvec, state,
-                       pidx, excl, unit_base, pw, pu, c);
+  LAUNCH_VEC(lamb_moments_kernel, aligned16(p, g, m, v), ew_grid(nvec), st, p, g, m, v, nvec, state, pidx, excl,
+             unit_base, pw, pu, lamb_consts(beta1, beta2, eps, wd));
   return (int)hipGetLastError();
 }
 
@@ -589,14 +583,8 @@ MI_API int mi_lamb_apply(float* p, const float* m, const float* v, void* p16, in
                          double beta2, double eps, double wd, hipStream_t st) {
   if (n < 0 || (n & 63)) return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
-  const LambConsts c = {(float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                        (float)wd};
   const int64_t nvec = n >> 2;
-  if (aligned16(p, m, v) && ((uintptr_t)p16 & 7) == 0)
-    hipLaunchKernelGGL(lamb_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(NT), 0, st, p, m, v, (bf16_t*)p16, nvec,
-                       state, pidx, excl, q, unit_base, c);
-  else
-    hipLaunchKernelGGL(lamb_apply_kernel<false>, dim3(ew_grid(nvec)), dim3(NT), 0, st, p, m, v, (bf16_t*)p16, nvec,
-                       state, pidx, excl, q, unit_base, c);
+  LAUNCH_VEC(lamb_apply_kernel, aligned16(p, m, v) && aligned8(p16), ew_grid(nvec), st, p, m, v, (bf16_t*)p16, nvec,
+             state, pidx, excl, q, unit_base, lamb_consts(beta1, beta2, eps, wd));
   return (int)hipGetLastError();
 }

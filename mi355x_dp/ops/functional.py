@@ -18,6 +18,7 @@ through autograd as usual (works with stock ``torch.nn.parallel.DDP``).
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import NamedTuple
 
@@ -727,6 +728,27 @@ def cross_entropy(logits, target, label_smoothing=0.0):
 
 
 # ================================================================= optimizer
+def _f32(x) -> float:
+    """host fallbacks: ``x`` rounded to fp32, the way the launchers round the constants they pass"""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def _check_f32(n, *tensors):
+    for t in tensors:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+
+
+def _clip_coef_host(state, sumsq, max_norm, grad_scale) -> float:
+    """host fallback of the prep kernels' clip coefficient (``clip_grad_norm_``): 1 without
+    ``max_norm``, else ``state[2]`` = the total norm and min(1, max_norm / (total + 1e-6))"""
+    if max_norm is None:
+        return 1.0
+    total = grad_scale * math.sqrt(float(sumsq.reshape(-1)[0]))
+    state[2] = total
+    c = float(max_norm) / (total + 1e-6)
+    return 1.0 if c > 1.0 else c  # NaN stays NaN, like torch's clamp(max=1)
+
+
 def sgd_flat_(params, grads, momentum_buf, params_bf16, lr, momentum=0.0, dampening=0.0, weight_decay=0.0,
               nesterov=False, first_step=False, grad_scale=1.0):
     """One fused SGD update over flat fp32 buffers (+ bf16 compute-copy refresh)."""
@@ -784,7 +806,7 @@ def grad_sqnorm_(segments, out, partials=None):
     assert partials.dtype == torch.float64 and partials.numel() >= sum(blocks) and out.dtype == torch.float64
     st, slot = stream_of(out), 0
     for x, nb in zip(segments, blocks):
-        assert x.dtype == torch.float32 and x.is_contiguous()
+        _check_f32(x.numel(), x)
         _lib.call("mi_grad_sqnorm_partial", ptr(x), x.numel(), ctypes.c_void_p(partials.data_ptr() + 8 * slot), st)
         slot += nb
     _lib.call("mi_grad_sqnorm_final", ptr(partials), slot, ptr(out), st)
@@ -798,17 +820,11 @@ def adamw_prep_(state, sumsq, beta1, beta2, weight_decay, max_norm=None, grad_sc
     (``torch.nn.utils.clip_grad_norm_``).  No host read."""
     clip = max_norm is not None
     if not state.is_cuda:
-        import math
         with torch.no_grad():
             t = float(state[0]) + 1.0
             lr = float(state[1])
             bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
-            coef = 1.0
-            if clip:
-                total = grad_scale * math.sqrt(float(sumsq.reshape(-1)[0]))
-                c = float(max_norm) / (total + 1e-6)
-                coef = 1.0 if c > 1.0 else c  # NaN stays NaN, like torch's clamp(max=1)
-                state[2] = total
+            coef = _clip_coef_host(state, sumsq, max_norm, grad_scale)
             state[0] = t
             state[3] = coef
             state[4] = lr / bc1
@@ -833,9 +849,8 @@ def adamw_flat_(params, grads, exp_avg, exp_avg_sq, params_bf16, state, beta1, b
     if not params.is_cuda:
         with torch.no_grad():
             s = state.tolist()
-            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
-            g = grads * f32(s[6])
-            decayed = params * f32(1.0 - s[7])
+            g = grads * _f32(s[6])
+            decayed = params * _f32(1.0 - s[7])
             if decay_map is None:
                 params.copy_(decayed)
             else:
@@ -843,13 +858,12 @@ def adamw_flat_(params, grads, exp_avg, exp_avg_sq, params_bf16, state, beta1, b
                 params.copy_(torch.where(units.repeat_interleave(64)[:n], decayed, params))
             exp_avg.mul_(beta1).add_(g, alpha=1 - beta1)
             exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1 - beta2)
-            denom = exp_avg_sq.sqrt().mul_(f32(s[5])).add_(eps)
-            params.addcdiv_(exp_avg, denom, value=-f32(s[4]))
+            denom = exp_avg_sq.sqrt().mul_(_f32(s[5])).add_(eps)
+            params.addcdiv_(exp_avg, denom, value=-_f32(s[4]))
             if params_bf16 is not None:
                 params_bf16.copy_(params)
         return
-    for t in (params, grads, exp_avg, exp_avg_sq):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    _check_f32(n, params, grads, exp_avg, exp_avg_sq)
     _lib.call("mi_adamw_flat", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), ptr(params_bf16), n,
               ptr(state), ptr(decay_map), int(unit_base), float(beta1), float(beta2), float(eps), stream_of(params))
 
@@ -874,6 +888,11 @@ def _unit_lookup(pidx, excl, q, unit_base, n):
     return rep(ex), rep(qu)
 
 
+def _unit_sq_host(t):
+    """host: fp64 sum of squares of every 64-element unit of ``t``"""
+    return t.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
+
+
 def seg_sqnorm_units_(x, part, y=None, part_y=None):
     """Pass 1 of the segmented norms: ``part[u]`` (float64) = sum of squares of the fp32 elements
     ``x[64 u : 64 u + 64]``; with ``y`` also ``part_y[u]`` from ``y`` in the same launch.  The bits of
@@ -886,10 +905,9 @@ def seg_sqnorm_units_(x, part, y=None, part_y=None):
         with torch.no_grad():
             for src, dst in ((x, part), (y, part_y)):
                 if src is not None:
-                    dst[:n // SEG_UNIT] = src.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
+                    dst[:n // SEG_UNIT] = _unit_sq_host(src)
         return
-    for t in (x, y):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    _check_f32(n, *(t for t in (x, y) if t is not None))
     assert part.is_contiguous() and (part_y is None or part_y.is_contiguous())
     _lib.call("mi_seg_sqnorm_units", ptr(x), ptr(y), n, ptr(part), ptr(part_y), stream_of(x))
 
@@ -955,8 +973,7 @@ def lamb_trust_(sums, excl, q):
 def _check_units(n, pidx, unit_base, *tensors):
     assert n % SEG_UNIT == 0, "layer-wise kernels take whole 64-element units"
     assert pidx.dtype == torch.int32 and pidx.numel() >= unit_base + n // SEG_UNIT and unit_base >= 0
-    for t in tensors:
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    _check_f32(n, *tensors)
 
 
 def lars_flat_(params, grads, momentum_buf, params_bf16, state, pidx, excl, q, unit_base, momentum, weight_decay,
@@ -969,12 +986,11 @@ def lars_flat_(params, grads, momentum_buf, params_bf16, state, pidx, excl, q, u
     _check_units(n, pidx, unit_base, params, grads, momentum_buf)
     if not params.is_cuda:
         with torch.no_grad():
-            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
             ex, qe = _unit_lookup(pidx, excl, q, unit_base, n)
-            g = grads * f32(grad_scale)
-            d = torch.where(ex, g, qe * (g + f32(weight_decay) * params))
-            momentum_buf.mul_(f32(momentum)).add_(d)
-            params.sub_(f32(float(state[1])) * momentum_buf)
+            g = grads * _f32(grad_scale)
+            d = torch.where(ex, g, qe * (g + _f32(weight_decay) * params))
+            momentum_buf.mul_(_f32(momentum)).add_(d)
+            params.sub_(_f32(float(state[1])) * momentum_buf)
             if params_bf16 is not None:
                 params_bf16.copy_(params)
         return
@@ -988,15 +1004,9 @@ def lamb_prep_(state, sumsq, beta1, beta2, max_norm=None, grad_scale=1.0):
     given, the clip coefficient from the squared gradient norm ``sumsq`` (as ``adamw_prep_``)."""
     clip = max_norm is not None
     if not state.is_cuda:
-        import math
         with torch.no_grad():
             t = float(state[0]) + 1.0
-            coef = 1.0
-            if clip:
-                total = grad_scale * math.sqrt(float(sumsq.reshape(-1)[0]))
-                c = float(max_norm) / (total + 1e-6)
-                coef = 1.0 if c > 1.0 else c
-                state[2] = total
+            coef = _clip_coef_host(state, sumsq, max_norm, grad_scale)
             state[0] = t
             state[3] = coef
             state[4] = 1.0 - beta1 ** t
@@ -1009,9 +1019,8 @@ def lamb_prep_(state, sumsq, beta1, beta2, max_norm=None, grad_scale=1.0):
 
 
 def _lamb_u_host(params, exp_avg, exp_avg_sq, ex, state, eps, weight_decay):
-    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
-    r = (exp_avg / f32(float(state[4]))) / ((exp_avg_sq / f32(float(state[5]))).sqrt() + f32(eps))
-    return torch.where(ex, r, r + f32(weight_decay) * params)
+    r = (exp_avg / _f32(float(state[4]))) / ((exp_avg_sq / _f32(float(state[5]))).sqrt() + _f32(eps))
+    return torch.where(ex, r, r + _f32(weight_decay) * params)
 
 
 def lamb_moments_(params, grads, exp_avg, exp_avg_sq, state, pidx, excl, unit_base, part_w, part_u, beta1, beta2,
@@ -1026,14 +1035,13 @@ def lamb_moments_(params, grads, exp_avg, exp_avg_sq, state, pidx, excl, unit_ba
         assert t.dtype == torch.float64 and t.numel() >= n // SEG_UNIT and t.is_contiguous()
     if not params.is_cuda:
         with torch.no_grad():
-            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
             ex, _ = _unit_lookup(pidx, excl, None, unit_base, n)
-            g = grads * f32(float(state[6]))
-            exp_avg.mul_(f32(beta1)).add_(g, alpha=f32(1.0 - beta1))
-            exp_avg_sq.mul_(f32(beta2)).add_(g * g, alpha=f32(1.0 - beta2))
+            g = grads * _f32(float(state[6]))
+            exp_avg.mul_(_f32(beta1)).add_(g, alpha=_f32(1.0 - beta1))
+            exp_avg_sq.mul_(_f32(beta2)).add_(g * g, alpha=_f32(1.0 - beta2))
             u = _lamb_u_host(params, exp_avg, exp_avg_sq, ex, state, eps, weight_decay)
-            part_w[:n // SEG_UNIT] = params.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
-            part_u[:n // SEG_UNIT] = u.double().reshape(-1, SEG_UNIT).pow(2).sum(1)
+            part_w[:n // SEG_UNIT] = _unit_sq_host(params)
+            part_u[:n // SEG_UNIT] = _unit_sq_host(u)
         return
     _lib.call("mi_lamb_moments", ptr(params), ptr(grads), ptr(exp_avg), ptr(exp_avg_sq), n, ptr(state), ptr(pidx),
               ptr(excl), int(unit_base), ptr(part_w), ptr(part_u), float(beta1), float(beta2), float(eps),
@@ -1048,10 +1056,9 @@ def lamb_apply_(params, exp_avg, exp_avg_sq, params_bf16, state, pidx, excl, q, 
     _check_units(n, pidx, unit_base, params, exp_avg, exp_avg_sq)
     if not params.is_cuda:
         with torch.no_grad():
-            f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))  # noqa: E731
             ex, qe = _unit_lookup(pidx, excl, q, unit_base, n)
             u = _lamb_u_host(params, exp_avg, exp_avg_sq, ex, state, eps, weight_decay)
-            params.sub_((f32(float(state[1])) * qe) * u)
+            params.sub_((_f32(float(state[1])) * qe) * u)
             if params_bf16 is not None:
                 params_bf16.copy_(params)
         return

@@ -30,8 +30,8 @@ Design (MI355X-first):
     optimizer on the comm stream.  The next forward waits for them (a stream wait, no host sync)
     and refreshes the bf16 compute copy.  Same bytes on the wire as the all-reduce (RS + AG), 1/world
     of the optimizer work and state.  Gradients outside the own shards are undefined after the
-    sync, so only the flat optimizers (``FlatSGD``, or ``FlatAdamW`` of parallel/optim.py) can drive
-    this mode.
+    sync, so only the flat optimizers of parallel/optim.py (``FlatSGD``, ``FlatAdamW``, ``FlatLARS``,
+    ``FlatLAMB``) can drive this mode.
 """
 from __future__ import annotations
 
@@ -981,94 +981,3 @@ class _GradBucket:
 
     def gradients(self):
         return [p.grad for p in self.parameters()]
-
-
-class _FlatOptimizer:
-    """What the flat optimizers share: the packed optimizer-state segments and the shard metadata
-    of their per-rank checkpoints."""
-
-    def _init_segments(self, engine: DataParallel) -> int:
-        """``self.segments`` = (flat lo, flat hi, packed-state offset) per range this rank updates
-        (shard mode: its shard of every bucket, packed -- 1/world of the optimizer state; otherwise
-        the whole flat buffer).  Returns the packed size."""
-        self.engine = engine
-        self.segments = []
-        off = 0
-        for lo, hi in engine.shard_ranges if engine.sharded else [(0, engine.flat.numel)]:
-            self.segments.append((lo, hi, off))
-            off += hi - lo
-        return off
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.engine.zero_grad()
-
-    def _shard_meta(self):
-        """Which slice of the packed momentum belongs to which flat range: the bucket plan (flat
-        [lo, hi) of every bucket and of this rank's shard of it) depends on the planner settings
-        and, with calibrate=True, on timing -- a resume must see the same plan."""
-        e = self.engine
-        return {"rank": e.rank, "world": e.world_size, "numel": int(e.flat.numel),
-                "bucket_ranges": [[int(lo), int(hi)] for lo, hi in e.bucket_ranges],
-                "shard_ranges": [[int(lo), int(hi)] for lo, hi in e.shard_ranges]}
-
-    def _check_shard_meta(self, sd):
-        if not self.engine.sharded:
-            return
-        want, got = self._shard_meta(), sd.get("shard") or {}
-        if {k: got.get(k) for k in ("rank", "world")} != {"rank": want["rank"], "world": want["world"]}:
-            raise ValueError(f"optimizer shard (rank {got.get('rank')} of {got.get('world')}) does not match "
-                             f"this rank ({want['rank']} of {want['world']})")
-        for k in ("numel", "bucket_ranges", "shard_ranges"):
-            if got.get(k) != want[k]:
-                raise ValueError(f"optimizer shard checkpoint was written with a different bucket plan ({k} "
-                                 "differs): its packed momentum would pair with the wrong parameters; resume "
-                                 "with the same bucket_cap_mb / first / last / min bucket settings and without "
-                                 "calibrate=True")
-
-
-class FlatSGD(_FlatOptimizer):
-    """torch.optim.SGD semantics over the flat buffer in ONE fused kernel launch
-    (momentum + weight decay + 1/world + bf16 copy refresh)."""
-
-    def __init__(self, engine: DataParallel, lr: float, momentum: float = 0.0, dampening: float = 0.0,
-                 weight_decay: float = 0.0, nesterov: bool = False):
-        self.lr, self.momentum, self.dampening = lr, momentum, dampening
-        self.weight_decay, self.nesterov = weight_decay, nesterov
-        # shard mode: momentum only for this rank's shards, packed (1/world of the optimizer state)
-        off = self._init_segments(engine)
-        self.momentum_buf = torch.zeros(off, dtype=torch.float32, device=engine.flat.data.device) if momentum else None
-        self.steps = 0
-        self.param_groups = [dict(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                                  dampening=dampening)]
-
-    def step(self):
-        from mi355x_dp.ops.functional import sgd_flat_
-        self.engine.finish_gradient_sync(average=False)
-        g = self.param_groups[0]
-        f = self.engine.flat
-        for lo, hi, mo in self.segments:
-            mom = self.momentum_buf[mo:mo + hi - lo] if self.momentum_buf is not None else None
-            sgd_flat_(f.data[lo:hi], f.grad[lo:hi], mom, f.bf16[lo:hi] if f.bf16 is not None else None, g["lr"],
-                      g["momentum"], g["dampening"], g["weight_decay"], g["nesterov"], first_step=(self.steps == 0),
-                      grad_scale=self.engine.grad_scale)
-        if self.engine.sharded and self.engine.comm_on:
-            self.engine.gather_params()  # bf16 copy + transposed operands refreshed after the gather
-        else:
-            f.refresh_transposed()  # dgrad operands of every conv, one launch
-        self.steps += 1
-
-    def state_dict(self):
-        """In shard mode ``momentum_buf`` is this rank's packed shards (a per-rank optimizer
-        checkpoint, tagged with ``shard``)."""
-        sd = {"steps": self.steps, "param_groups": self.param_groups,
-              "momentum_buf": self.momentum_buf.detach().cpu() if self.momentum_buf is not None else None}
-        if self.engine.sharded:
-            sd["shard"] = self._shard_meta()
-        return sd
-
-    def load_state_dict(self, sd):
-        self._check_shard_meta(sd)
-        self.steps = sd["steps"]
-        self.param_groups = sd["param_groups"]
-        if sd.get("momentum_buf") is not None and self.momentum_buf is not None:
-            self.momentum_buf.copy_(sd["momentum_buf"])
