@@ -49,6 +49,9 @@ def main():
     ap.add_argument("--label-smoothing", type=float, default=0.0)
     ap.add_argument("--mixup-alpha", type=float, default=0.0, help="Mixup Beta(alpha, alpha); 0 = off")
     ap.add_argument("--cutmix-alpha", type=float, default=0.0, help="CutMix Beta(alpha, alpha); 0 = off")
+    ap.add_argument("--ema-decay", type=float, default=0.0, help="weight averaging (FlatEMA) decay; 0 = off")
+    ap.add_argument("--ema-warmup", type=float, default=None, help="d_t = min(decay, (1 + n) / (warmup + n))")
+    ap.add_argument("--ema-every", type=int, default=1, help="average on every k-th step only")
     a = ap.parse_args()
     t_job = time.time()
     import torch
@@ -74,7 +77,11 @@ def main():
     torch.manual_seed(a.seed)
     engine = DataParallel(get_model("resnet18", num_classes=1000).to(dev))
     opt = FlatSGD(engine, lr=a.lr, momentum=a.momentum)
-    B = a.global_batch // world
+    ema = None
+    if a.ema_decay > 0:
+        from mi355x_dp.parallel import FlatEMA
+        ema = FlatEMA(engine, decay=a.ema_decay, warmup=a.ema_warmup, update_every=a.ema_every)
+    B =a.global_batch // world
     shard = torch.arange(rank, imgs.shape[0], world, device=dev)   # DistributedSampler split
     steps = shard.numel() // B                                       # static shapes: drop the last partial batch
     if rank == 0:
@@ -101,6 +108,8 @@ def main():
             loss = cross_entropy(engine(x), yb, label_smoothing=a.label_smoothing)
         loss.backward()
         opt.step()
+        if ema is not None:
+            ema.update()  # captured with the step: its counters and weight live on the device
         return loss
 
     graphed, step_no = None, 0
@@ -156,6 +165,12 @@ def main():
         tl, acc = evaluate()
         if rank == 0:
             print(f"Test set: Average loss: {tl:.4f}, Accuracy: {acc:.2f}\n", flush=True)
+        if ema is not None:
+            with ema.applied():  # the averaged weights in place, on the same native kernels
+                etl, eacc = evaluate()
+            if rank == 0:
+                print(f"Test set (averaged weights, {ema.num_updates} updates): Average loss: {etl:.4f}, "
+                      f"Accuracy: {eacc:.2f}\n", flush=True)
     loop_s = time.time() - t_loop
     if rank == 0:
         imgs_trained = a.epochs * steps * B * world

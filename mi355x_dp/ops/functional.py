@@ -1067,6 +1067,74 @@ def lamb_apply_(params, exp_avg, exp_avg_sq, params_bf16, state, pidx, excl, q, 
               stream_of(params))
 
 
+# weight averaging on the flat buffer (csrc/kernels/ema.hip, parallel/ema.py).  Device state
+# block, float64:
+#   [0] calls c  [1] updates n  [2] w of this call (0 = this call skips)  [3] decay
+#   [4] d_t of the last call that updated
+EMA_STATE_LEN = 5
+
+
+def ema_prep_(state, warmup, every):
+    """Advance the call counter and derive this call's weight in ``state`` (layout above), all in
+    fp64::
+
+        c += 1
+        if c % every != 0:   w = 0                                       (n, d_t unchanged)
+        else:  d_t = decay if warmup is None or warmup <= 0 else min(decay, (1 + n) / (warmup + n))
+               w = 1 - d_t ;  n += 1
+
+    ``decay`` is read from ``state[3]``.  No host read."""
+    warmup = 0.0 if warmup is None else float(warmup)
+    every = int(every)
+    assert every >= 1 and state.dtype == torch.float64 and state.numel() >= EMA_STATE_LEN
+    if not state.is_cuda:
+        with torch.no_grad():
+            c = float(state[0]) + 1.0
+            state[0] = c
+            if int(c) % every != 0:
+                state[2] = 0.0
+                return
+            n, d = float(state[1]), float(state[3])
+            if warmup > 0.0:
+                d = min(d, (1.0 + n) / (warmup + n))
+            state[1] = n + 1.0
+            state[2] = 1.0 - d
+            state[4] = d
+        return
+    _lib.call("mi_ema_prep", ptr(state), warmup, every, stream_of(state))
+
+
+def ema_update_(ema, p, state):
+    """``ema += w * (p - ema)`` over two fp32 buffers of any length and 4-byte alignment, with
+    ``w = state[2]`` of ``ema_prep_`` rounded to fp32 (device: one fused multiply-add per element;
+    host: product and sum rounded separately).  ``w == 0`` leaves ``ema`` untouched."""
+    n = ema.numel()
+    _check_f32(n, ema, p)
+    if not ema.is_cuda:
+        with torch.no_grad():
+            w = float(state[2])
+            if w != 0.0:
+                ema.add_(torch.tensor(w, dtype=torch.float32) * (p - ema))
+        return
+    assert state.dtype == torch.float64 and state.numel() >= EMA_STATE_LEN
+    _lib.call("mi_ema_update", ptr(ema), ptr(p), n, ptr(state), stream_of(ema))
+
+
+def ema_swap_(a, b):
+    """Exchange two fp32 buffers of equal length in place as 32-bit patterns (NaN payloads, signed
+    zeros and denormals pass through): the exchange is its own inverse bit for bit."""
+    n = a.numel()
+    _check_f32(n, a, b)
+    if not a.is_cuda:
+        with torch.no_grad():
+            ai, bi = a.view(torch.int32), b.view(torch.int32)
+            t = ai.clone()
+            ai.copy_(bi)
+            bi.copy_(t)
+        return
+    _lib.call("mi_ema_swap", ptr(a), ptr(b), n, stream_of(a))
+
+
 def cast_bf16_(src, dst):
     if not src.is_cuda:
         dst.copy_(src)

@@ -1,7 +1,8 @@
 """The flat optimizers: ``FlatSGD``, ``FlatAdamW``, ``FlatLARS`` and ``FlatLAMB`` update the engine's
 flat fp32 master buffer with fused launches per segment and refresh the bf16 copy in the same pass.
-``_FlatOptimizer`` holds what all four share (segments, layout checks, the step tail, shard
-metadata), ``_DeviceStateOptimizer`` what the three with a device state block share (``lr`` upload,
+``_FlatSegments`` holds the packed segments, their layout checks and the shard metadata (shared
+with ``FlatEMA``), ``_FlatOptimizer`` what all four add (flat slices, the step tail),
+``_DeviceStateOptimizer`` what the three with a device state block share (``lr`` upload,
 the global-norm pass, checkpoints), ``_LayerwiseOptimizer`` the segmented norms of LARS and LAMB.
 
 ``FlatAdamW``: torch.optim.AdamW semantics over the engine's flat buffers, with global-norm
@@ -69,9 +70,10 @@ def default_no_decay(name: str, param: torch.Tensor) -> bool:
     return param.ndim <= 1
 
 
-class _FlatOptimizer:
-    """What the flat optimizers share: the packed optimizer-state segments with their layout
-    checks and slices, the step tail and the shard metadata of their per-rank checkpoints."""
+class _FlatSegments:
+    """Per-element state packed to the ranges of the flat buffer this rank updates -- what the flat
+    optimizers and ``FlatEMA`` (ema.py) share: the segments with their layout checks and slices,
+    and the shard metadata of their per-rank checkpoints."""
 
     # which segment ends must be multiples of 64 elements (with every flat offset): None = no
     # requirement, "lo" = the starts, "lo_hi" = starts and ends
@@ -94,33 +96,11 @@ class _FlatOptimizer:
             raise ValueError(f"{who}: shard boundaries must be multiples of 64 elements")
         return off
 
-    def _names(self):
-        """the module's name of every parameter of the flat buffer ("" where it has none)"""
-        names = {id(p): n for n, p in self.engine.module.named_parameters()}
-        return [names.get(id(p), "") for p in self.engine.flat.params]
-
-    def _flat(self, seg):
-        """(master, gradient, bf16 copy or None) slices of one segment"""
-        lo, hi, _off = seg
-        f = self.engine.flat
-        return f.data[lo:hi], f.grad[lo:hi], f.bf16[lo:hi] if f.bf16 is not None else None
-
     @staticmethod
     def _packed(t, seg):
         """one segment's slice of a packed state tensor"""
         lo, hi, off = seg
         return t[off:off + hi - lo]
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.engine.zero_grad()
-
-    def _finish(self):
-        """the step tail: publish the updated parameters to the compute copies"""
-        e = self.engine
-        if e.sharded and e.comm_on:
-            e.gather_params()  # bf16 copy + transposed operands refreshed after the gather
-        else:
-            e.flat.refresh_transposed()  # dgrad operands of every conv, one launch
 
     def _shard_meta(self):
         """Which slice of the packed momentum belongs to which flat range: the bucket plan (flat
@@ -144,6 +124,33 @@ class _FlatOptimizer:
                                  "differs): its packed momentum would pair with the wrong parameters; resume "
                                  "with the same bucket_cap_mb / first / last / min bucket settings and without "
                                  "calibrate=True")
+
+
+class _FlatOptimizer(_FlatSegments):
+    """What the flat optimizers share beyond ``_FlatSegments``: the parameter names, the flat
+    slices of a segment and the step tail."""
+
+    def _names(self):
+        """the module's name of every parameter of the flat buffer ("" where it has none)"""
+        names = {id(p): n for n, p in self.engine.module.named_parameters()}
+        return [names.get(id(p), "") for p in self.engine.flat.params]
+
+    def _flat(self, seg):
+        """(master, gradient, bf16 copy or None) slices of one segment"""
+        lo, hi, _off = seg
+        f = self.engine.flat
+        return f.data[lo:hi], f.grad[lo:hi], f.bf16[lo:hi] if f.bf16 is not None else None
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.engine.zero_grad()
+
+    def _finish(self):
+        """the step tail: publish the updated parameters to the compute copies"""
+        e = self.engine
+        if e.sharded and e.comm_on:
+            e.gather_params()  # bf16 copy + transposed operands refreshed after the gather
+        else:
+            e.flat.refresh_transposed()  # dgrad operands of every conv, one launch
 
 
 class FlatSGD(_FlatOptimizer):

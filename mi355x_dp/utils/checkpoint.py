@@ -11,7 +11,8 @@
   rank (map_location to the local device) with ``weights_only=True``.  An optimizer whose state is
   sharded over ranks (``FlatSGD`` under ``DataParallel(shard_optimizer=True)``: each rank holds the
   momentum of its own shards only) is written by EVERY rank to ``<path>.optim-rank<r>-of-<w>``;
-  the main file records the world size and loading checks it.
+  the main file records the world size and loading checks it.  ``ema=`` (a ``FlatEMA``) travels
+  the same way: under ``"ema"`` in the main file, or per rank in ``<path>.ema-rank<r>-of-<w>``.
 """
 from __future__ import annotations
 
@@ -56,6 +57,10 @@ def optim_shard_path(path: str, rank: int, world: int) -> str:
     return f"{path}.optim-rank{rank}-of-{world}"
 
 
+def ema_shard_path(path: str, rank: int, world: int) -> str:
+    return f"{path}.ema-rank{rank}-of-{world}"
+
+
 def _drop_state(model):
     """the model's dropout / stochastic-depth state (ops.transformer.DropState: seed, rank, step) --
     not a module, so not part of ``state_dict()``; looked up through a DDP-style ``.module`` wrapper"""
@@ -67,12 +72,17 @@ def _drop_state(model):
 
 
 def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, step: int = 0, epoch: int = 0,
-                    extra: Optional[Dict[str, Any]] = None) -> Optional[str]:
+                    extra: Optional[Dict[str, Any]] = None, ema=None) -> Optional[str]:
     osd = optimizer.state_dict() if optimizer is not None else None
     sharded = isinstance(osd, dict) and "shard" in osd
     if sharded:
         os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
         _atomic_save(osd, optim_shard_path(path, _rank(), _world()))
+    esd = ema.state_dict() if ema is not None else None
+    ema_sharded = isinstance(esd, dict) and "shard" in esd
+    if ema_sharded:
+        os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
+        _atomic_save(esd, ema_shard_path(path, _rank(), _world()))
     if _rank() != 0:
         if dist.is_available() and dist.is_initialized():
             dist.barrier()
@@ -87,6 +97,8 @@ def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, step: int
         state["rng_cuda"] = torch.cuda.get_rng_state()
     if optimizer is not None:
         state["optimizer"] = {"sharded_over": _world()} if sharded else osd
+    if ema is not None:
+        state["ema"] = {"sharded_over": _world()} if ema_sharded else esd
     ds = _drop_state(model)
     if ds is not None:
         state["drop_state"] = ds.state_dict()
@@ -99,7 +111,8 @@ def save_checkpoint(path: str, model: torch.nn.Module, optimizer=None, step: int
     return path
 
 
-def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, map_location=None) -> Dict[str, Any]:
+def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, map_location=None,
+                    ema=None) -> Dict[str, Any]:
     state = torch.load(path, map_location=map_location or "cpu", weights_only=True)
     model.load_state_dict(state["model"])
     if optimizer is not None and "optimizer" in state:
@@ -111,6 +124,17 @@ def load_checkpoint(path: str, model: torch.nn.Module, optimizer=None, map_locat
             osd = torch.load(optim_shard_path(path, _rank(), _world()), map_location=map_location or "cpu",
                              weights_only=True)
         optimizer.load_state_dict(osd)
+    if ema is not None:
+        if "ema" not in state:
+            raise ValueError(f"checkpoint {path} holds no averaged weights (it was saved without ema=)")
+        esd = state["ema"]
+        if isinstance(esd, dict) and "sharded_over" in esd:
+            if esd["sharded_over"] != _world():
+                raise ValueError(f"checkpoint averaged weights are sharded over {esd['sharded_over']} ranks, "
+                                 f"this job has {_world()}")
+            esd = torch.load(ema_shard_path(path, _rank(), _world()), map_location=map_location or "cpu",
+                             weights_only=True)
+        ema.load_state_dict(esd)
     ds = _drop_state(model)
     if ds is not None and "drop_state" in state:
         ds.load_state_dict(state["drop_state"])

@@ -20,6 +20,15 @@ read, m, v written = 24; apply: p, m, v read, p and bf16 written = 18); the fp64
 8 B per 64 elements and array.
 
     python tools/bench_optim.py --suite layerwise [--out profiles/layerwise_optim.json]
+
+``--suite ema`` times ``FlatEMA.update()`` against ``torch._foreach_lerp_`` over the parameters as
+separate tensors (what ``AveragedModel`` runs), one ``lerp_`` over the whole flat buffer (the
+bytes-equal floor of a library call), the enter + exit of ``FlatEMA.applied()`` and the two kernels
+alone.  The update moves 12 B per element (p and ema read, ema written), the exchange 16.
+``--ema-ab-lib`` names a kernel library built with the other cache policy of the update kernel
+(``-DMI_EMA_NT=0/1``); its kernel is then timed in the same alternation.
+
+    python tools/bench_optim.py --suite ema [--ema-ab-lib LIB] [--out profiles/raw/ema_flat.json]
 """
 import argparse
 import json
@@ -172,6 +181,95 @@ def bench_layerwise(name, steps, rounds, warmup):
             "kernels": _rows(kms, {k: b for k, (_, b) in kernels.items()})}
 
 
+def bench_ema(name, steps, rounds, warmup, ab_lib=None):
+    """``FlatEMA.update()`` against ``torch._foreach_lerp_`` over the parameters as separate tensors
+    (what ``AveragedModel`` runs) and one ``lerp_`` over the whole flat buffer, the exchange of
+    ``applied()``, and the update kernel of this build against the one of ``ab_lib`` (a library
+    built with the other cache policy), all interleaved in one process"""
+    import ctypes
+    from mi355x_dp import ops
+    from mi355x_dp.models import get_model
+    from mi355x_dp.ops import _lib
+    from mi355x_dp.parallel import DataParallel, FlatEMA
+    torch.manual_seed(0)
+    eng = DataParallel(get_model(name).cuda())
+    f = eng.flat
+    n = f.numel
+    ema = FlatEMA(eng, decay=0.999)
+    w = 1.0 - ema.decay
+    live = [p.data for p in f.params]
+    avg_list = [p.detach().clone() for p in live]  # separate allocations, as a deep copy of the module has
+    avg_flat = f.data.clone()
+    kernel_avg = f.data.clone()
+    state = ema.state.clone()
+    state[2] = w  # the kernels alone: no prep launch, a fixed weight
+
+    def applied():
+        with ema.applied():
+            pass
+
+    def policy(lib):
+        return "nontemporal" if lib.mi_ema_nontemporal() else "plain"
+
+    lib = _lib.load(True)
+    kernels = {f"update_kernel_{policy(lib)} (this build)": lambda: ops.ema_update_(kernel_avg, f.data, state)}
+    if ab_lib:
+        alt = ctypes.CDLL(ab_lib)
+        alt.mi_ema_update.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                      ctypes.c_void_p]
+        alt.mi_ema_update.restype = ctypes.c_int
+        assert policy(alt) != policy(lib), "--ema-ab-lib must be built with the other MI_EMA_NT"
+        alt_avg = f.data.clone()
+
+        def alt_update():
+            rc = alt.mi_ema_update(_lib.ptr(alt_avg), _lib.ptr(f.data), n, _lib.ptr(state), _lib.stream_of(alt_avg))
+            assert rc == 0, rc
+        kernels[f"update_kernel_{policy(alt)} (A/B build)"] = alt_update
+    sides = {"flat_ema_update (prep + 1 launch)": ema.update,
+             "foreach_lerp (separate tensors)": lambda: torch._foreach_lerp_(avg_list, live, w),
+             "lerp_ (whole flat buffer)": lambda: avg_flat.lerp_(f.data, w),
+             **kernels,
+             "swap_kernel": lambda: ops.ema_swap_(kernel_avg, avg_flat),
+             "applied() enter + exit": applied}
+    # update: p and ema read, ema written; swap: both read and written; applied(): two exchanges
+    # (the two refreshes of the bf16 and transposed copies it also pays are not counted as bytes)
+    payload = sum(p.numel() for p in f.params)
+    nbytes = {k: 12 * n for k in sides}
+    nbytes["foreach_lerp (separate tensors)"] = 12 * payload  # no alignment padding between tensors
+    nbytes["swap_kernel"] = 16 * n
+    nbytes["applied() enter + exit"] = 32 * n
+    for fn in sides.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in sides}
+    for _ in range(rounds):  # alternate the sides
+        for k, fn in sides.items():
+            ms[k].append(timed(fn, steps))
+
+    # Back-to-back calls find their operands in the 256 MB last-level cache where they fit (the
+    # ResNet-50 buffers do); in a training step a whole forward and backward run between two
+    # updates.  Cold: 1 GiB written before every single call, one event pair per call.
+    flush = torch.empty(1 << 28, dtype=torch.float32, device="cuda")
+    cold = {k: fn for k, fn in sides.items() if k not in ("swap_kernel", "applied() enter + exit")}
+    cms = {k: [] for k in cold}
+    for _ in range(rounds):
+        for k, fn in cold.items():
+            pairs = []
+            for _ in range(20):
+                flush.zero_()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                pairs.append((a, b))
+            torch.cuda.synchronize()
+            cms[k].append(statistics.median(a.elapsed_time(b) for a, b in pairs))
+    return {"model": name, "flat_numel": n, "payload_numel": payload, "tensors": len(f.params),
+            "steps_per_measurement": steps, "rounds": rounds, "results": _rows(ms, nbytes),
+            "cold_cache_single_calls": _rows(cms, nbytes)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="vitb16,resnet50")
@@ -179,14 +277,20 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--suite", default="adamw", choices=["adamw", "layerwise"])
+    ap.add_argument("--suite", default="adamw", choices=["adamw", "layerwise", "ema"])
+    ap.add_argument("--ema-ab-lib", default=None,
+                    help="--suite ema: a kernel library built with the other cache policy, e.g. "
+                         "mi355x_dp.build.build_kernels(variant='emant', defines=('MI_EMA_NT=1',))")
     a = ap.parse_args()
     if a.steps < 100:
         ap.error("--steps must be at least 100")
+    if a.suite == "ema":
+        models = [bench_ema(m, a.steps, a.rounds, a.warmup, a.ema_ab_lib) for m in a.models.split(",")]
+    else:
+        models = [(bench_layerwise if a.suite == "layerwise" else bench_model)(m, a.steps, a.rounds, a.warmup)
+                  for m in a.models.split(",")]
     out = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "hip": torch.version.hip,
-           "suite": a.suite,
-           "models": [(bench_layerwise if a.suite == "layerwise" else bench_model)(m, a.steps, a.rounds, a.warmup)
-                      for m in a.models.split(",")]}
+           "suite": a.suite, "models": models}
     line = json.dumps(out)
     print(line)
     if a.out:
