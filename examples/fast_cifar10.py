@@ -52,7 +52,14 @@ def main():
     ap.add_argument("--ema-decay", type=float, default=0.0, help="weight averaging (FlatEMA) decay; 0 = off")
     ap.add_argument("--ema-warmup", type=float, default=None, help="d_t = min(decay, (1 + n) / (warmup + n))")
     ap.add_argument("--ema-every", type=int, default=1, help="average on every k-th step only")
+    ap.add_argument("--image-size", type=int, default=32, help="train and evaluate at S x S (resized on the device)")
+    ap.add_argument("--rrc-scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="RandomResizedCrop area range (default 0.08 1.0 once the resized path is on)")
+    ap.add_argument("--random-erase", type=float, default=None, metavar="P", help="RandomErasing probability")
     a = ap.parse_args()
+    # any of the three switches the input pass from the shift crop to BatchCropper + augment_resized
+    resized = a.image_size != 32 or a.rrc_scale is not None or a.random_erase is not None
+    S = a.image_size
     t_job = time.time()
     import torch
     import torch.distributed as dist
@@ -64,7 +71,7 @@ def main():
     if world > 1:
         dist.init_process_group("nccl", device_id=dev)
     from mi355x_dp.models import get_model
-    from mi355x_dp.ops import MixedTarget, augment, augment_mix, cross_entropy
+    from mi355x_dp.ops import MixedTarget, augment, augment_mix, augment_resized, cross_entropy
     from mi355x_dp.parallel import DataParallel, FlatSGD
 
     xtr, ytr, xte, yte = load_data(a.data, a.n_train, a.n_test, a.seed)
@@ -90,7 +97,7 @@ def main():
 
     u8 = torch.empty((B, 32, 32, 3), dtype=torch.uint8, device=dev)
     yb = torch.empty((B,), dtype=torch.long, device=dev)
-    x = torch.empty((B, 8, 32, 32), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
+    x = torch.empty((B, 8, S, S), dtype=torch.bfloat16, device=dev, memory_format=torch.channels_last)
 
     # Mixup / CutMix: the mixing parameters are drawn on the host per step, the mixing itself and the
     # pair target (static buffers, rewritten before every replay) come out of the augmentation pass
@@ -99,6 +106,13 @@ def main():
         from mi355x_dp.data.mix import BatchMixer
         mixer = BatchMixer(a.mixup_alpha, a.cutmix_alpha, seed=a.seed, rank=rank, device=dev)
         target = MixedTarget(torch.empty_like(yb), torch.empty_like(yb), torch.ones(B, device=dev))
+    # RandomResizedCrop / RandomErasing: per-image boxes drawn on the host per step, like the mixing
+    # parameters; the CutMix box lives in output (S x S) coordinates
+    cropper = None
+    if resized:
+        from mi355x_dp.data.crops import BatchCropper
+        cropper = BatchCropper(S, scale=tuple(a.rrc_scale or (0.08, 1.0)), erase_prob=a.random_erase or 0.0,
+                               seed=a.seed, rank=rank, device=dev)
 
     def core():
         engine.zero_grad()
@@ -118,7 +132,11 @@ def main():
         nonlocal graphed, step_no
         torch.index_select(imgs, 0, idx, out=u8)
         torch.index_select(labels, 0, idx, out=yb)
-        if mixer is not None:
+        if cropper is not None:
+            mix = mixer.params(step_no, B, S, S) if mixer is not None else None
+            augment_resized(u8, S, 8, MEAN, STD, cropper.params(step_no, B, 32, 32), mix=mix,
+                            labels=yb if mixer is not None else None, out=x, target=target)
+        elif mixer is not None:
             augment_mix(u8, yb, 8, MEAN, STD, mixer.params(step_no, B, 32, 32), pad=4, flip=True,
                         seed=a.seed * 1000003 + step_no, out=x, target=target)
         else:
@@ -136,7 +154,11 @@ def main():
         loss, correct = 0.0, 0
         with torch.no_grad():
             for i in range(0, timgs.shape[0], 1000):
-                xt = augment(timgs[i:i + 1000], 8, MEAN, STD, pad=4, flip=True, seed=99 + i)
+                if cropper is not None:  # the evaluation transform: the whole image, resized
+                    n = min(1000, timgs.shape[0] - i)
+                    xt = augment_resized(timgs[i:i + n], S, 8, MEAN, STD, cropper.center_params(n, 32, 32))
+                else:
+                    xt = augment(timgs[i:i + 1000], 8, MEAN, STD, pad=4, flip=True, seed=99 + i)
                 out = engine(xt).float()
                 y = tlabels[i:i + 1000]
                 loss += float(torch.nn.functional.nll_loss(out, y, reduction="sum"))  # reference: nll on logits

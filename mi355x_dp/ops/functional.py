@@ -1156,6 +1156,19 @@ def checksum(x: torch.Tensor) -> float:
 _AUG_CONST = {}
 
 
+def _aug_const(dev, C, out_channels, mean, std):
+    """(mean, 1 / std) as fp32 [max(Cout, C)] tensors on ``dev``: device constants built once and
+    shared by the input-pipeline ops (no per-step host->device copies)."""
+    key = (str(dev), max(out_channels, C), C, tuple(mean), tuple(std))
+    if key not in _AUG_CONST:
+        mean_t = torch.zeros(max(out_channels, C), dtype=torch.float32, device=dev)
+        stdinv_t = torch.ones(max(out_channels, C), dtype=torch.float32, device=dev)
+        mean_t[:C] = torch.tensor(mean, dtype=torch.float32)
+        stdinv_t[:C] = 1.0 / torch.tensor(std, dtype=torch.float32)
+        _AUG_CONST[key] = (mean_t, stdinv_t)
+    return _AUG_CONST[key]
+
+
 def augment(images_u8, out_channels, mean, std, pad=4, flip=True, seed=0, out=None):
     """uint8 NHWC [N,H,W,C] -> bf16 channels_last [N,Cout,H,W]: random crop (zero padding
     ``pad``) + horizontal flip + normalize, all on the GPU (replaces the reference's per-sample
@@ -1163,14 +1176,7 @@ def augment(images_u8, out_channels, mean, std, pad=4, flip=True, seed=0, out=No
     buffer (the input of a captured HIP-graph step)."""
     N, H, W, C = images_u8.shape
     dev = images_u8.device
-    key = (str(dev), max(out_channels, C), C, tuple(mean), tuple(std))
-    if key not in _AUG_CONST:  # device constants built once (no per-step host->device copies)
-        mean_t = torch.zeros(max(out_channels, C), dtype=torch.float32, device=dev)
-        stdinv_t = torch.ones(max(out_channels, C), dtype=torch.float32, device=dev)
-        mean_t[:C] = torch.tensor(mean, dtype=torch.float32)
-        stdinv_t[:C] = 1.0 / torch.tensor(std, dtype=torch.float32)
-        _AUG_CONST[key] = (mean_t, stdinv_t)
-    mean_t, stdinv_t = _AUG_CONST[key]
+    mean_t, stdinv_t = _aug_const(dev, C, out_channels, mean, std)
     if not images_u8.is_cuda:
         x = images_u8.float().div(255.0).permute(0, 3, 1, 2)
         x = (x - mean_t[:C].view(1, C, 1, 1)) * stdinv_t[:C].view(1, C, 1, 1)
@@ -1182,6 +1188,27 @@ def augment(images_u8, out_channels, mean, std, pad=4, flip=True, seed=0, out=No
     _lib.call("mi_augment", ptr(images_u8.contiguous()), ptr(out), N, H, W, C, out_channels, int(pad), int(flip),
               seed & 0xFFFFFFFF, ptr(mean_t), ptr(stdinv_t), stream_of(images_u8))
     return out
+
+
+def _mix_cpu(x, labels, params):
+    """Host reference of the Mixup / CutMix rule on already augmented values ``x`` [N, C, H, W]."""
+    N, _, H, W = x.shape
+    partner, lam = params.partner.long(), params.lam.float().clone()
+    ok = (partner >= 0) & (partner < N)
+    partner = torch.where(ok, partner, torch.arange(N))
+    lam[~ok] = 1.0
+    box = params.box.long()
+    y0, y1 = box[:, 0].clamp(0, H), box[:, 1].clamp(0, H)
+    x0, x1 = box[:, 2].clamp(0, W), box[:, 3].clamp(0, W)
+    cut = ok & (y1 > y0) & (x1 > x0)
+    hh, ww = torch.arange(H).view(1, H, 1), torch.arange(W).view(1, 1, W)
+    inbox = (cut.view(N, 1, 1) & (hh >= y0.view(N, 1, 1)) & (hh < y1.view(N, 1, 1))
+             & (ww >= x0.view(N, 1, 1)) & (ww < x1.view(N, 1, 1))).unsqueeze(1)
+    lam_px = torch.where(cut, torch.ones_like(lam), lam).view(N, 1, 1, 1)
+    xb = x[partner]
+    x = torch.where(inbox, xb, lam_px * x + (1 - lam_px) * xb)
+    lam = torch.where(cut, 1.0 - ((y1 - y0) * (x1 - x0)).float() / float(H * W), lam)
+    return x, MixedTarget(labels.long(), labels.long()[partner], lam)
 
 
 def augment_mix(images_u8, labels, out_channels, mean, std, params, pad=4, flip=True, seed=0, out=None, target=None):
@@ -1200,22 +1227,7 @@ def augment_mix(images_u8, labels, out_channels, mean, std, params, pad=4, flip=
     dev = images_u8.device
     if not images_u8.is_cuda:
         x = augment(images_u8, out_channels, mean, std, pad=pad, flip=flip, seed=seed)
-        partner, lam = params.partner.long(), params.lam.float().clone()
-        ok = (partner >= 0) & (partner < N)
-        partner = torch.where(ok, partner, torch.arange(N))
-        lam[~ok] = 1.0
-        box = params.box.long()
-        y0, y1 = box[:, 0].clamp(0, H), box[:, 1].clamp(0, H)
-        x0, x1 = box[:, 2].clamp(0, W), box[:, 3].clamp(0, W)
-        cut = ok & (y1 > y0) & (x1 > x0)
-        hh, ww = torch.arange(H).view(1, H, 1), torch.arange(W).view(1, 1, W)
-        inbox = (cut.view(N, 1, 1) & (hh >= y0.view(N, 1, 1)) & (hh < y1.view(N, 1, 1))
-                 & (ww >= x0.view(N, 1, 1)) & (ww < x1.view(N, 1, 1))).unsqueeze(1)
-        lam_px = torch.where(cut, torch.ones_like(lam), lam).view(N, 1, 1, 1)
-        xb = x[partner]
-        x = torch.where(inbox, xb, lam_px * x + (1 - lam_px) * xb)
-        lam = torch.where(cut, 1.0 - ((y1 - y0) * (x1 - x0)).float() / float(H * W), lam)
-        return x, MixedTarget(labels.long(), labels.long()[partner], lam)
+        return _mix_cpu(x, labels, params)
     if labels.dtype != torch.int64 or labels.shape != (N,) or labels.device != dev:
         raise ValueError(f"augment_mix: labels must be an int64 [{N}] tensor on {dev}")
     partner, lam, box = params.partner, params.lam, params.box
@@ -1226,14 +1238,7 @@ def augment_mix(images_u8, labels, out_channels, mean, std, params, pad=4, flip=
         raise ValueError(f"augment_mix: params.lam must be a contiguous fp32 [{N}] tensor on {dev}")
     if not (box.dtype == torch.int32 and box.shape == (N, 4) and box.device == dev and box.is_contiguous()):
         raise ValueError(f"augment_mix: params.box must be a contiguous int32 [{N}, 4] tensor on {dev}")
-    key = (str(dev), max(out_channels, C), C, tuple(mean), tuple(std))
-    if key not in _AUG_CONST:  # augment's device constants, shared with it
-        mean_t = torch.zeros(max(out_channels, C), dtype=torch.float32, device=dev)
-        stdinv_t = torch.ones(max(out_channels, C), dtype=torch.float32, device=dev)
-        mean_t[:C] = torch.tensor(mean, dtype=torch.float32)
-        stdinv_t[:C] = 1.0 / torch.tensor(std, dtype=torch.float32)
-        _AUG_CONST[key] = (mean_t, stdinv_t)
-    mean_t, stdinv_t = _AUG_CONST[key]
+    mean_t, stdinv_t = _aug_const(dev, C, out_channels, mean, std)
     if out is None:
         out = torch.empty((N, out_channels, H, W), dtype=BF16, device=dev, memory_format=CL)
     elif not (out.shape == (N, out_channels, H, W) and out.dtype == BF16 and out.is_contiguous(memory_format=CL)):
@@ -1249,3 +1254,104 @@ def augment_mix(images_u8, labels, out_channels, mean, std, params, pad=4, flip=
               ptr(lam), ptr(box), ptr(target.y_a), ptr(target.y_b), ptr(target.lam), N, H, W, C, out_channels,
               int(pad), int(flip), seed & 0xFFFFFFFF, ptr(mean_t), ptr(stdinv_t), stream_of(images_u8))
     return out, target
+
+
+def _resized_cpu(images_u8, Ho, Wo, out_channels, geo, mean_t, stdinv_t):
+    """Host reference of the resample of ``augment_resized``: fp32 [N, Cout, Ho, Wo]."""
+    N, Hs, Ws, C = images_u8.shape
+    crop, flip, erase = geo.crop.long(), geo.flip.long(), geo.erase.long()
+    top, left = crop[:, 0].clamp(0, Hs - 1), crop[:, 1].clamp(0, Ws - 1)
+    ch = torch.minimum(crop[:, 2].clamp(min=1), Hs - top)
+    cw = torch.minimum(crop[:, 3].clamp(min=1), Ws - left)
+
+    def axis(o, length, n_out):  # o [N, n_out], length [N] -> first tap, second tap, weight of the second
+        num = ((2 * o + 1) * length[:, None] - n_out).clamp(min=0)
+        i0 = num // (2 * n_out)
+        return i0, torch.minimum(i0 + 1, length[:, None] - 1), (num % (2 * n_out)).float() / float(2 * n_out)
+
+    oh = torch.arange(Ho).expand(N, Ho)
+    ow = torch.arange(Wo).expand(N, Wo)
+    y0, y1, ly = axis(oh, ch, Ho)
+    x0, x1, lx = axis(torch.where(flip[:, None] != 0, Wo - 1 - ow, ow), cw, Wo)
+    img, n = images_u8.float(), torch.arange(N).view(N, 1, 1)
+    ys, xs = [(top[:, None] + y)[:, :, None] for y in (y0, y1)], [(left[:, None] + x)[:, None, :] for x in (x0, x1)]
+    a, b, d, e = img[n, ys[0], xs[0]], img[n, ys[0], xs[1]], img[n, ys[1], xs[0]], img[n, ys[1], xs[1]]
+    lx, ly = lx.view(N, 1, Wo, 1), ly.view(N, Ho, 1, 1)
+    up, dn = a + lx * (b - a), d + lx * (e - d)
+    v = (up + ly * (dn - up)).div(255.0)  # [N, Ho, Wo, C]
+    v = (v - mean_t[:C]) * stdinv_t[:C]
+    ey0, ey1 = erase[:, 0].clamp(0, Ho).view(N, 1, 1), erase[:, 1].clamp(0, Ho).view(N, 1, 1)
+    ex0, ex1 = erase[:, 2].clamp(0, Wo).view(N, 1, 1), erase[:, 3].clamp(0, Wo).view(N, 1, 1)
+    erased = (oh.view(N, Ho, 1) >= ey0) & (oh.view(N, Ho, 1) < ey1) & (ow.view(N, 1, Wo) >= ex0) & (ow.view(N, 1, Wo) < ex1)
+    v = torch.where(erased.unsqueeze(-1), torch.zeros((), dtype=v.dtype), v)
+    x = torch.zeros((N, max(out_channels, C), Ho, Wo), dtype=torch.float32)
+    x[:, :C] = v.permute(0, 3, 1, 2)
+    return x
+
+
+def augment_resized(images_u8, size, out_channels, mean, std, geo, mix=None, labels=None, out=None, target=None):
+    """uint8 NHWC [N,Hs,Ws,C] -> bf16 channels_last [N,Cout,Ho,Wo] through a per-image crop box and a
+    bilinear resample: RandomResizedCrop, resize + centre crop and RandomErasing in ``augment``'s one
+    pass (``csrc/kernels/resample.hip``).  Returns ``x``, or ``(x, MixedTarget)`` when ``mix`` is given.
+
+    ``size`` is ``Ho`` or ``(Ho, Wo)``.  ``geo`` carries the per-image, device-resident geometry
+    (``data.crops.BatchCropper``): ``crop`` int32 [N, 4] = (top, left, height, width) in source
+    pixels, ``flip`` int32 [N], ``erase`` int32 [N, 4] = (y0, y1, x0, x1) in output pixels (empty: no
+    erasing).  The value of an output pixel is "crop, then ``F.interpolate(mode="bilinear",
+    align_corners=False, antialias=False)``", with source coordinates in exact integer arithmetic
+    (a box of the output's size returns the source pixels), then the flip, ``augment``'s
+    normalisation, and 0 inside the image's erase box.  Every box is clipped to its domain by the
+    kernel.  ``mix`` (``data.mix.MixParams``, with ``labels`` int64 [N]) applies ``augment_mix``'s
+    Mixup / CutMix rule to those values; image and partner each use their own crop, flip and erase
+    box.  ``out`` / ``target``: static buffers to write into (the inputs of a captured HIP-graph step).
+
+    Not done here: antialiased downscaling (torchvision's tensor default is ``antialias=True``; it
+    matters only when the box is much larger than the output), bicubic resampling, sources of
+    unequal size within one batch, RandAugment / TrivialAugment.
+
+    Host tensors take a torch implementation of the same semantics (fp32 output)."""
+    N, Hs, Ws, C = images_u8.shape
+    Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    dev = images_u8.device
+    if (mix is None) != (labels is None):
+        raise ValueError("augment_resized: mix and labels go together")
+    mean_t, stdinv_t = _aug_const(dev, C, out_channels, mean, std)
+    if not images_u8.is_cuda:
+        x = _resized_cpu(images_u8, Ho, Wo, out_channels, geo, mean_t, stdinv_t)
+        return x if mix is None else _mix_cpu(x, labels, mix)
+    crop, flip, erase = geo.crop, geo.flip, geo.erase
+    for name, t, shape in (("crop", crop, (N, 4)), ("flip", flip, (N,)), ("erase", erase, (N, 4))):
+        if not (t.dtype == torch.int32 and t.shape == shape and t.device == dev and t.is_contiguous()):
+            raise ValueError(f"augment_resized: geo.{name} must be a contiguous int32 {list(shape)} tensor on {dev}")
+    if out is None:
+        out = torch.empty((N, out_channels, Ho, Wo), dtype=BF16, device=dev, memory_format=CL)
+    elif not (out.shape == (N, out_channels, Ho, Wo) and out.dtype == BF16 and out.is_contiguous(memory_format=CL)):
+        raise ValueError("augment_resized(out=...) needs a bf16 channels_last [N, Cout, Ho, Wo] tensor")
+    if mix is None:
+        if target is not None:
+            raise ValueError("augment_resized(target=...) needs mix")
+        mix_args = (ptr(None),) * 7
+    else:
+        if labels.dtype != torch.int64 or labels.shape != (N,) or labels.device != dev:
+            raise ValueError(f"augment_resized: labels must be an int64 [{N}] tensor on {dev}")
+        partner, lam, box = mix.partner, mix.lam, mix.box
+        if not (partner.dtype == torch.int32 and partner.shape == (N,) and partner.device == dev
+                and partner.is_contiguous()):
+            raise ValueError(f"augment_resized: mix.partner must be a contiguous int32 [{N}] tensor on {dev}")
+        if not (lam.dtype == torch.float32 and lam.shape == (N,) and lam.device == dev and lam.is_contiguous()):
+            raise ValueError(f"augment_resized: mix.lam must be a contiguous fp32 [{N}] tensor on {dev}")
+        if not (box.dtype == torch.int32 and box.shape == (N, 4) and box.device == dev and box.is_contiguous()):
+            raise ValueError(f"augment_resized: mix.box must be a contiguous int32 [{N}, 4] tensor on {dev}")
+        if target is None:
+            target = MixedTarget(torch.empty_like(labels), torch.empty_like(labels),
+                                 torch.empty(N, dtype=torch.float32, device=dev))
+        else:
+            for t, dt in ((target.y_a, torch.int64), (target.y_b, torch.int64), (target.lam, torch.float32)):
+                if not (t.dtype == dt and t.shape == (N,) and t.device == dev and t.is_contiguous()):
+                    raise ValueError(
+                        f"augment_resized(target=...) needs contiguous int64 / int64 / fp32 [{N}] tensors on {dev}")
+        mix_args = (ptr(labels.contiguous()), ptr(partner), ptr(lam), ptr(box), ptr(target.y_a), ptr(target.y_b),
+                    ptr(target.lam))
+    _lib.call("mi_augment_resized", ptr(images_u8.contiguous()), ptr(out), ptr(crop), ptr(flip), ptr(erase), *mix_args,
+              N, Hs, Ws, Ho, Wo, C, out_channels, ptr(mean_t), ptr(stdinv_t), stream_of(images_u8))
+    return out if mix is None else (out, target)
