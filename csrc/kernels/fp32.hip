@@ -446,15 +446,17 @@ __global__ __launch_bounds__(FT) void maxpoolf_bwd_kernel(const float* __restric
   }
 }
 
-// y[n][c] = mean over HW of x[n][hw][c]; one thread per (n, c), HW summed in order
+// y[n][c] = mean over HW of x[n][hw][c]; one thread per (n, c), HW summed in order.  The sum is kept
+// in fp64 (like the BatchNorm reductions): an fp32 running sum of 3136 terms is off by 1.6e-6 of the
+// largest mean, the load-bound loop does not notice the wider add
 __global__ __launch_bounds__(FT) void gapf_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int Nb,
                                                       int HW, int C) {
   const int i = blockIdx.x * FT + threadIdx.x;
   if (i >= Nb * C) return;
   const int n = i / C, c = i % C;
-  float s = 0.f;
-  for (int j = 0; j < HW; ++j) s += x[((int64_t)n * HW + j) * C + c];
-  y[i] = s / HW;
+  double s = 0.0;
+  for (int j = 0; j < HW; ++j) s += (double)x[((int64_t)n * HW + j) * C + c];
+  y[i] = (float)(s / HW);
 }
 
 __global__ __launch_bounds__(FT) void gapf_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, int Nb,

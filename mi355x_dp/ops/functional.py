@@ -1173,7 +1173,15 @@ def augment(images_u8, out_channels, mean, std, pad=4, flip=True, seed=0, out=No
     """uint8 NHWC [N,H,W,C] -> bf16 channels_last [N,Cout,H,W]: random crop (zero padding
     ``pad``) + horizontal flip + normalize, all on the GPU (replaces the reference's per-sample
     PIL transforms, cifar10-distributed-smddp-gpu.py:55-62).  ``out``: write into a static
-    buffer (the input of a captured HIP-graph step)."""
+    buffer (the input of a captured HIP-graph step).
+
+    Per image n, one hash of ``(seed mod 2^32, n)`` gives offsets dy, dx in [-pad, pad] and the flip
+    bit; output pixel (h, w) is source pixel (h + dy, (W - 1 - w if flipped else w) + dx), i.e. pad,
+    crop at (pad + dy, pad + dx), then flip.  The border the padding adds is 0 in the output
+    (filled after normalising, not (0 - mean) / std), as are channels C..Cout-1.
+
+    Host tensors: only the normalisation, as fp32 [N,C,H,W] -- no crop, no flip, no channel fill,
+    whatever ``pad``, ``flip``, ``seed`` and ``out_channels`` say."""
     N, H, W, C = images_u8.shape
     dev = images_u8.device
     mean_t, stdinv_t = _aug_const(dev, C, out_channels, mean, std)
